@@ -16,7 +16,13 @@ scaling, value = N_0 * I / T of the one job.  --mode replicas instead runs an in
 per rank (seed 11 + rank, no collective; weak scaling).  Barrier + max-over-ranks timing.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c4|c5]
-                    [--mode sharded|replicas] [--cpu-baseline auto|reference|port|full|none]
+                    [--mode sharded|replicas] [--dump-outputs DIR]
+                    [--full [--cpu-baseline auto|reference|port|full|none]]
+
+A plain run sets up, warms up, times the K steps and prints the result line (its per-class
+figures come from the timed steps' own counters).  --full adds what takes work of its own: the
+last step's output against the committed full-size fixture ("parity"; a mismatch exits 1) and
+the CPU baseline ("cpu_baseline").  --dump-outputs DIR writes what the last timed step computed.
 """
 from __future__ import annotations
 
@@ -281,8 +287,9 @@ def cpu_baseline(eng, mode, n0, d, iters, min_sim, counter0, trace):
                 "c1_measured": c1}
     out = dict({"unit": "k-mers·iterations/s", "cores": threads, "kind": kind, "c1_measured": c1},
                **sampled)
-    # the reference's whole loop as measured once on a GPU box's host (bench.py --cpu-baseline
-    # full, committed in profiles/cpu_reference_full.json), beside this run's sampled estimate
+    # the reference's whole loop as measured once on a GPU box's host (bench.py --full
+    # --cpu-baseline full, committed in profiles/cpu_reference_full.json), beside this run's
+    # sampled estimate
     committed = reference_full_committed(n0, d, iters)
     if committed:
         committed["ratio_sampled_to_full"] = round(t_loop / committed["loop_s"], 4)
@@ -364,6 +371,37 @@ def check_parity(config, trace, counter, result):
                       md5(ids) == fx["md5_ids"])
     out["ok"] = all(v for key, v in out.items() if key in ("trace", "counter", "md5"))
     return out
+
+
+DUMP_SEED = 20240607   # the fixed sample of a large output
+DUMP_ROW_BYTES = 24 << 20  # sampled cluster rows (float32)
+DUMP_MAX_INTS = 1 << 19    # sampled member offsets / ids (4 MiB each as float64)
+
+
+def dump_outputs(path, trace, counter, result):
+    """Write what the last timed step returned to its caller as <path>/<name>.npy (float32 /
+    float64; integers are below 2^53, so float64 holds them exactly): the N_t trace, the rng
+    counter, and of the engine's result the cluster rows, member offsets and member ids.  An array
+    beyond its cap is a fixed, seeded sample (the sampled positions written beside it as
+    <name>_index), which keeps the files of every config below 64 MB in all."""
+    os.makedirs(path, exist_ok=True)
+    rows, off, ids = result()
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {"trace": np.asarray(trace, dtype=np.float64),
+           "counter": np.asarray([counter], dtype=np.float64)}
+    max_rows = DUMP_ROW_BYTES // (4 * max(1, rows.shape[1]))
+    for name, a, cap in (("rows", rows, max_rows), ("member_offsets", off, DUMP_MAX_INTS),
+                         ("member_ids", ids, DUMP_MAX_INTS)):
+        if a.shape[0] > cap:
+            at = np.sort(rng.choice(a.shape[0], size=cap, replace=False))
+            out[name + "_index"] = at.astype(np.float64)
+            a = a[at]
+        out[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    total = sum(a.nbytes for a in out.values())
+    log(f"dumped {', '.join(sorted(out))} to {path} ({total / 1e6:.1f} MB)")
+    return total
 
 
 def pmc_traffic(config, kernel):
@@ -579,9 +617,15 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also check the last step against the committed full-size fixture "
+                         "(a mismatch exits 1) and measure the CPU baseline (--cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--cpu-baseline", default="auto",
                     choices=["auto", "reference", "port", "full", "none"],
-                    help="full: the reference's whole main loop timed once (C2: minutes)")
+                    help="with --full; full: the reference's whole main loop timed once "
+                         "(C2: minutes)")
     ap.add_argument("--mode", default="sharded", choices=["sharded", "replicas"],
                     help="N>1: one problem sharded over the ranks (C3) or one problem per rank")
     ap.add_argument("--phases", action="store_true",
@@ -632,9 +676,13 @@ def main():
 
     if rank != 0:
         return
-    # outside the timed region: the last step's output against the committed full-size fixture
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, trace, counter, eng.result)
+    # outside the timed region (--full): the last step's output against the committed full-size
+    # fixture
     parity = (check_parity(args.config, trace, counter, eng.result)
-              if (world == 1 or sharded) and not args.iterations else {"checked": False})
+              if args.full and (world == 1 or sharded) and not args.iterations
+              else {"checked": False})
     if parity.get("checked"):
         log(f"parity vs {parity['fixture']}: {'ok' if parity['ok'] else 'MISMATCH'}")
     value = (1 if sharded else world) * n0 * iters * args.steps / elapsed
@@ -662,7 +710,7 @@ def main():
                         "bytes_per_step": loop_bytes / args.steps,
                         "note": "SURVEY.md 8(d) algorithmic bytes of the whole loop / step time"}
     cpu = None
-    if world == 1:
+    if args.full and world == 1:
         try:
             cpu = cpu_baseline(eng, args.cpu_baseline, n0, d, iters, min_sim, counter0, trace)
         except Exception as e:  # the baseline is reported, never required

@@ -21,7 +21,7 @@ run() {  # name seconds cmd...
 }
 B="python bench.py --steps 1 --warmup 0 --cpu-baseline none --option progress=25"
 if [ "$1" != pmc ] && [ "$1" != c45 ]; then
-  run c2_bench 300 python bench.py --steps 3 --warmup 1
+  run c2_bench 300 python bench.py --steps 3 --warmup 1 --full
   run c2_stats 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/c2_stats -o run -- $B
 fi
 if [ "$1" = pmc ] || [ "$1" = all ]; then
