@@ -1485,7 +1485,9 @@ static int run_single(klsh_ctx* ctx, float& threshold, float sim_step, int it_be
       st->project_ms += elapsed(ctx->ev[e0], ctx->ev[e0 + 1]);
       st->project_timed_launches += 1;
     }
-    if (rec && ctx->phase_timing) st->sort_ms += elapsed(ctx->ev[1], ctx->ev[5]);
+    // from the end of THIS iteration's projection: ev[7] when it was queued behind the previous
+    // compaction (ev[1] then belongs to another iteration's projection)
+    if (rec && ctx->phase_timing) st->sort_ms += elapsed(ctx->ev[e0 + 1], ctx->ev[5]);
     st->project_launches += 1;
     st->sum_rows += n;
     st->sum_proj_bits += n * (uint64_t)h;

@@ -18,6 +18,8 @@ from conftest import GOLDEN, ROOT, golden
 pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, GOLDEN)
+import make_golden_thr  # noqa: E402
+from make_golden_thr import threshold_rows  # noqa: E402
 
 
 def same_bits(a, b):
@@ -338,6 +340,21 @@ def test_pcluster_matches_reference(engine, name):
     engine.load_rows(z["rows"])
     engine.pcluster(float(z["thr"]))
     assert_same_result(engine.result(), z["out_rows"], z["out_off"], z["out_ids"])
+
+
+@pytest.mark.parametrize("per_class", [0, 1])
+@pytest.mark.parametrize("b,d", make_golden_thr.PCLUSTER_THR_SHAPES)
+def test_pcluster_threshold_domain_matches_reference(engine, b, d, per_class):
+    """The reference's own results over the threshold domain (tests/golden/make_golden_thr.py)."""
+    rows, cases = make_golden_thr.load_pcluster_thr(b, d)
+    with options(engine, tail_merge_rows=per_class):
+        for thr, out_rows, out_off, out_ids in cases:
+            engine.load_rows(rows)
+            engine.pcluster(thr)
+            try:
+                assert_same_result(engine.result(), out_rows, out_off, out_ids)
+            except AssertionError as ex:
+                raise AssertionError(f"thr={thr!r}") from ex
 
 
 @pytest.mark.parametrize("b,d,groups,noise,thr", [
@@ -662,6 +679,49 @@ def test_pcluster_threshold_ties(engine, oracle, b, d, step):
         assert_same_result(engine.result(), *oracle.pcluster(rows, float(thr)))
 
 
+def seq_sim_matrix(rows):
+    """seq_sim for every ordered pair (a current, c candidate) at once: the same fp32 operations
+    in the same order, numpy rounding each one."""
+    x = np.ascontiguousarray(rows, np.float32)
+    b, d = x.shape
+    dot = np.zeros((b, b), np.float32)
+    n2 = np.zeros(b, np.float32)
+    for k in range(d):
+        dot = dot + x[:, k, None] * x[None, :, k]
+        n2 = n2 + x[:, k] * x[:, k]
+    s = np.sqrt(n2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return dot / (s[:, None] * s[None, :])
+
+
+@pytest.mark.parametrize("b,d", [(40, 16), (64, 64), (200, 32), (200, 64), (500, 16), (100, 512)])
+def test_pcluster_threshold_ties_extremes(engine, oracle, b, d):
+    """test_pcluster_threshold_ties away from 0.8: thresholds at, and one ulp either side of, the
+    round trip fl(1 - fl(1 - sim)) of the run's most negative similarity, of the one closest to 0
+    and of the largest one below 1 — ties in the plain decider regime (s* <= 0), at the edge of
+    the fast one and next to 1 — by default and through the per-class launches."""
+    rng = np.random.default_rng(b * 5 + d)
+    rows = clustered(rng, b, d, max(2, b // 20), 0.08)
+    f = np.float32
+    sim = seq_sim_matrix(rows)
+    assert sim[1, 0] == seq_sim(rows[1], rows[0])
+    off_diag = sim[~np.eye(b, dtype=bool)]
+    picks = [off_diag.min(), off_diag[np.argmin(np.abs(off_diag))], off_diag[off_diag < 1].max()]
+    for s in picks:
+        tie = f(f(1) - f(f(1) - s))
+        for thr in (np.nextafter(tie, f(-np.inf), dtype=f), tie, np.nextafter(tie, f(np.inf), dtype=f)):
+            want = oracle.pcluster(rows, float(thr))
+            for per_class in (0, 1):
+                with options(engine, tail_merge_rows=per_class):
+                    engine.load_rows(rows)
+                    engine.pcluster(float(thr))
+                    got = engine.result()
+                try:
+                    assert_same_result(got, *want)
+                except AssertionError as ex:
+                    raise AssertionError(f"thr={float(thr)!r} per_class={per_class}") from ex
+
+
 @pytest.mark.parametrize("b,d", [(33, 64), (1000, 16), (5000, 8)])
 def test_pcluster_identical_rows(engine, oracle, b, d):
     """Degenerate bucket (every row identical): the wave kernel merges i into j = 0 each step."""
@@ -671,9 +731,128 @@ def test_pcluster_identical_rows(engine, oracle, b, d):
     assert_same_result(engine.result(), *oracle.pcluster(rows, 0.95))
 
 
+# ------------------------------------------------- p_cluster over the whole threshold domain ---
+# The product takes any float as the threshold (-N is read with atof and the loop walks it from
+# 0.95 to min_similarity).  make_decider gives two regimes: `fast` (s* in
+# [2^-60, 2^60]: rcp quotient bounds, Gram tiles, fp16 screens) and the plain one (s* <= 0, tiny,
+# huge, infinite or NaN: g_lo = g_hi = 0, so every certified screen must stand aside).
+_F = np.float32
+ONE_PRED = float(np.nextafter(_F(1), _F(0)))
+ONE_SUCC = float(np.nextafter(_F(1), _F(2)))
+T_ALL = [0.0, -0.0, -0.25, -1.0, -1.5, 1e-30, 0.05, 0.5, ONE_PRED, 1.0, ONE_SUCC, 1.5,
+         float("inf"), float("-inf"), float("nan")]
+T_BIG = [0.0, -0.25, 0.05, 1.0]
+T_WIDE = [0.0, -0.25, 0.05, 1.0, ONE_SUCC, float("nan")]
+# the oracle's own result must be non-degenerate here (b >= 9) ...
+T_SOME = [0.0, -0.0, -0.25, 1e-30, 0.05, 0.5, ONE_PRED, 1.0]
+# ... and nothing may merge here
+T_NONE = [float("inf"), float("nan"), 1.5]
+_thr_runs = {}
+
+
+def _thr_key(thr):
+    return np.float32(thr).view(np.uint32).item()
+
+
+def threshold_run(oracle, b, d, thresholds):
+    """threshold_rows(b, d) and the oracle's p_cluster result per threshold, computed once per
+    shape and shared by every launch variant; the conditions on the oracle's own output (some but
+    not all rows merge / nothing merges) are asserted here, from the oracle alone."""
+    if (b, d) not in _thr_runs:
+        rng = np.random.default_rng(b * 1009 + d)
+        _thr_runs[b, d] = (threshold_rows(rng, b, d, max(2, b // 4)), {})
+    rows, want = _thr_runs[b, d]
+    for thr in thresholds:
+        if _thr_key(thr) in want:
+            continue
+        res = oracle.pcluster(rows, thr)
+        survivors = res[0].shape[0]
+        if b >= 9 and any(_thr_key(thr) == _thr_key(t) for t in T_SOME):
+            assert 1 < survivors < b, (b, d, thr, survivors)
+        if any(_thr_key(thr) == _thr_key(t) for t in T_NONE):
+            assert survivors == b, (b, d, thr, survivors)
+        want[_thr_key(thr)] = res
+    return rows, want
+
+
+def check_threshold_run(engine, oracle, b, d, thresholds, **opts):
+    rows, want = threshold_run(oracle, b, d, thresholds)
+    with options(engine, **opts):
+        for thr in thresholds:
+            engine.load_rows(rows)
+            engine.pcluster(thr)
+            try:
+                assert_same_result(engine.result(), *want[_thr_key(thr)])
+            except AssertionError as ex:
+                raise AssertionError(f"b={b} d={d} thr={thr!r} {opts}") from ex
+
+
+@pytest.mark.parametrize("d,small_screen", [(64, 1), (64, 0), (32, 1), (32, 0), (16, 1), (8, 1),
+                                            (13, 1)])
+@pytest.mark.parametrize("b", [2, 3, 5, 9, 17, 33, 64])
+def test_pcluster_thresholds_small_runs(engine, oracle, b, d, small_screen):
+    """Runs of 2..64 rows (every G-lane group class) over T_ALL: the fp16 small-run screen
+    (d = 64, 32; screen_ok's gate on the decider) on and off, the packed group merges at d = 16 and
+    8, the wide ones at d = 13.  Through k_merge_tail (the default for a run this short) and through
+    the per-class launches."""
+    check_threshold_run(engine, oracle, b, d, T_ALL, small_screen=small_screen)
+    check_threshold_run(engine, oracle, b, d, T_ALL, small_screen=small_screen, tail_merge_rows=1)
+
+
+@pytest.mark.parametrize("per_class", [0, 1])
+@pytest.mark.parametrize("d", [64, 32, 16])
+@pytest.mark.parametrize("b", [65, 128, 129, 192, 193, 384, 385, 896])
+def test_pcluster_thresholds_big_runs(engine, oracle, b, d, per_class):
+    """Runs of 65..896 rows at every class edge over T_ALL: k_merge_tail's big-run workgroups with
+    its tail_big_screen gate (default) and the per-class k_merge_big (tail_merge_rows = 1), whose
+    Gram tiles and re-decides are gated on the decider."""
+    check_threshold_run(engine, oracle, b, d, T_ALL, tail_merge_rows=per_class)
+
+
+@pytest.mark.parametrize("d", [32, 16])
+@pytest.mark.parametrize("b", [385, 896])
+def test_pcluster_thresholds_long_385_896(engine, oracle, b, d):
+    """long_runs = 4 hands the 385..896-row runs to k_merge_long, which only takes them with a fast
+    decider: the other thresholds fall back to k_merge_big<896>.  (Its bit matrices exist once the
+    context holds 897 slots or more, as any input with such runs does: reserved here first.)"""
+    engine.load_rows(np.zeros((897, d), np.float32))
+    check_threshold_run(engine, oracle, b, d, T_ALL, tail_merge_rows=1, long_runs=4)
+
+
+@pytest.mark.parametrize("b,d,long_runs,huge_fold", [
+    (b, d, lr, 0) for b in (897, 1537, 4097) for d in (32, 16) for lr in (4, 0)] + [
+    (1537, 32, 1, 1), (897, 16, 0, 1)])
+def test_pcluster_thresholds_over_896(engine, oracle, b, d, long_runs, huge_fold):
+    """Runs over 896 rows at d = 16 / 32 over T_BIG: k_merge_long (fast decider) or its fall-back
+    to the huge walk (long_runs = 4), the huge walk alone (long_runs = 0), and the fold into the
+    385..896-row kernel (huge_fold = 1)."""
+    check_threshold_run(engine, oracle, b, d, T_BIG, tail_merge_rows=1, long_runs=long_runs,
+                        huge_fold=huge_fold)
+
+
+@pytest.mark.parametrize("per_class", [0, 1])
+def test_pcluster_thresholds_over_896_d64(engine, oracle, per_class):
+    check_threshold_run(engine, oracle, 1200, 64, T_BIG, tail_merge_rows=per_class)
+
+
+@pytest.mark.parametrize("gram", [8, 32, 0])
+@pytest.mark.parametrize("b", [17, 33, 64])
+def test_pcluster_thresholds_wide_gram(engine, oracle, b, gram):
+    """d = 512 group merges with the bf16x3 Gram tiles (wide_gram, gated on the decider) or the
+    exact chains."""
+    check_threshold_run(engine, oracle, b, 512, T_WIDE, wide_gram=gram, tail_merge_rows=1)
+    check_threshold_run(engine, oracle, b, 512, T_WIDE, wide_gram=gram)
+
+
+@pytest.mark.parametrize("b,d", [(100, 512), (300, 130), (40, 100)])
+@pytest.mark.parametrize("per_class", [0, 1])
+def test_pcluster_thresholds_wide_rows(engine, oracle, b, d, per_class):
+    check_threshold_run(engine, oracle, b, d, T_WIDE, tail_merge_rows=per_class)
+
+
 # ------------------------------------------------------------------------------- Cluster ----
 CLUSTER_CASES = ["cluster_d16", "cluster_d64", "cluster_d12", "cluster_d8_init", "cluster_nested",
-                 "cluster_nested_small"]
+                 "cluster_nested_small"] + sorted(make_golden_thr.CLUSTER_THR_CASES)
 
 
 @pytest.mark.parametrize("name", CLUSTER_CASES)
@@ -726,6 +905,111 @@ def test_cluster_random_vs_oracle(engine, oracle, n, d, groups, iters, bthr):
     assert np.array_equal(trace, o_trace)
     assert counter == o_counter
     assert_same_result(engine.result(), o_rows, o_off, o_ids)
+
+
+def loop_thresholds(min_sim, iters):
+    """The threshold of each iteration, in the loop's own float arithmetic (cluster.cc:190-192)."""
+    f = np.float32
+    step = f(f(f(0.95) - f(min_sim)) / f(iters))
+    out, thr = [], f(0.95)
+    for _ in range(iters):
+        out.append(thr)
+        thr = f(thr - step)
+    return out
+
+
+@pytest.mark.parametrize("n,d,groups,noise,iters,bthr", [
+    (30000, 64, 400, 0.3, 12, 1000000),
+    (30000, 32, 3000, 0.5, 12, 1000000),
+    (20000, 16, 2000, 0.5, 10, 2000),     # nested
+    (8000, 512, 300, 0.3, 8, 1000000),
+    (20000, 13, 2000, 0.5, 10, 1000000),
+])
+@pytest.mark.parametrize("min_sim", [-0.5, 0.0, 0.5, 0.97, 1.3])
+def test_cluster_min_similarity_vs_oracle(engine, oracle, min_sim, n, d, groups, noise, iters, bthr):
+    """The loop at other min_similarity values than 0.8: the threshold walks from 0.95 down to and
+    below 0 (the plain decider regime inside the loop, with runs of every class), to 0.5, or UP to
+    0.97 and 1.3 (nothing merges past 1) — by default (the queued tail and k_merge_tail), through
+    the per-class launches and with the host-driven tail: the oracle's trace, counter and result
+    bits every time."""
+    rng = np.random.default_rng(n + d + 17)
+    rows = clustered(rng, n, d, groups, noise)
+    want = oracle.cluster(rows, min_sim, iters, bthr, 777, 3)
+    if min_sim == -0.5:
+        # trace[t] = N_t, the rows iteration t starts with
+        plain = [t for t, thr in enumerate(loop_thresholds(min_sim, iters))
+                 if thr <= 0 and want[3][t] >= 65]
+        assert len(plain) >= 2, (list(want[3]), plain)
+    for opts in ({}, {"tail_merge_rows": 1}, {"tail_batch": 0}):
+        with options(engine, **opts):
+            engine.load_rows(rows)
+            trace, counter, _ = engine.cluster(min_sim, iters, bthr, 777, 3)
+            got = engine.result()
+        assert np.array_equal(trace, want[3]) and counter == want[4], (opts, trace, want[3])
+        assert_same_result(got, *want[:3])
+
+
+# sort_ms (HIP events from the end of the iteration's projection to the end of its sort, launch
+# gaps included) against the sort kernels' own stamp spans of the same call.  The event pair
+# brackets the kernels on one stream, so sort_ms cannot be below the stamps but for the clocks'
+# granularity (10 % allowed).  The sort is one of four phases of comparable cost (projection,
+# sort, merge, compaction), so a span that reached back into another iteration would be several
+# times the sort's own: at most 3 times the stamps (1.2 measured on an MI355X).
+SORT_MS_RATIO_MIN, SORT_MS_RATIO_MAX = 0.9, 3.0
+
+
+@pytest.mark.parametrize("n,d,groups,bthr", [(100000, 64, 1500, 1000000), (20000, 16, 300, 2000)])
+@pytest.mark.parametrize("hip_events,phase_timing,tail_batch", [(1, 0, 0), (1, 0, 1), (0, 1, 1),
+                                                                (1, 1, 1)])
+def test_cluster_timing_options_vs_oracle(engine, oracle, n, d, groups, bthr, hip_events,
+                                          phase_timing, tail_batch):
+    """Options hip_events (event pairs around the projection of every host-driven iteration, the
+    one queued behind the previous compaction included: spec_ev) and phase_timing (syncs between
+    the phases, no queued batches: what bench.py --full runs) change the loop's control flow, not
+    its result: the oracle's trace, counter and bits, and every host-driven projection launch
+    timed.  The queued tail batches carry no events (klsh.h: project_timed_launches), and at these
+    sizes they are the whole loop, so hip_events alone runs once with tail_batch = 0 (every
+    iteration host-driven, all of them timed) and once with the batches on."""
+    rng = np.random.default_rng(n + d + 23)
+    rows = clustered(rng, n, d, groups, 0.05)
+    if bthr < n:  # three tight groups over bthr rows each (nested in the first iteration: the
+        # queued projection is discarded and redone) among loose ones that keep merging later
+        rows[: n // 2] = clustered(rng, n // 2, d, 3, 0.02)
+        rows[n // 2:] = clustered(rng, n - n // 2, d, groups, 0.3)
+        rows = rows[rng.permutation(n)]
+    want = _timing_want(oracle, rows, n, d, bthr)
+    with options(engine, hip_events=hip_events, phase_timing=phase_timing, tail_batch=tail_batch):
+        engine.load_rows(rows)
+        trace, counter, st = engine.cluster(0.8, 12, bthr, 91, 2)
+        got = engine.result()
+    assert np.array_equal(trace, want[3]) and counter == want[4]
+    assert_same_result(got, *want[:3])
+    assert st["project_launches"] == st["iterations"] == 12
+    if phase_timing or not tail_batch:
+        assert st["project_timed_launches"] == st["project_launches"]
+        assert st["project_ms"] > 0.0
+    else:
+        # host-driven (timed) until the first iteration the tail batches take: N_t below 2^20 and
+        # within bthr, two or more iterations left (klsh.h: tail_merge_rows); they keep the rest
+        host = next((t for t in range(12)
+                     if 2 <= want[3][t] <= min(bthr, (1 << 20) - 1) and 12 - t >= 2), 12)
+        assert st["project_timed_launches"] == host
+    if bthr < n:
+        assert st["nested_calls"] > 0
+    if phase_timing:
+        stamp = st["kern"]["sort"]["ms"]
+        print(f"sort_ms {st['sort_ms']:.4f} stamps {stamp:.4f} ratio {st['sort_ms'] / stamp:.3f}")
+        assert stamp > 0.0
+        assert SORT_MS_RATIO_MIN * stamp <= st["sort_ms"] <= SORT_MS_RATIO_MAX * stamp
+
+
+_timing_wants = {}
+
+
+def _timing_want(oracle, rows, n, d, bthr):
+    if (n, d) not in _timing_wants:
+        _timing_wants[n, d] = oracle.cluster(rows, 0.8, 12, bthr, 91, 2)
+    return _timing_wants[n, d]
 
 
 @pytest.mark.parametrize("n,d,groups,iters,bthr,long_runs", [

@@ -138,6 +138,39 @@ def test_sharded_random_vs_single(engine, world, n, d, groups, iters, bthr):
         assert_same(outs[r], results[r], *ref)
 
 
+def test_sharded_negative_min_similarity_vs_single(engine):
+    """min_similarity = -0.5: the threshold walks below 0, where the merge decider leaves its fast
+    regime (no certified screens) — sharded in every iteration, against the single-GPU call."""
+    rng = np.random.default_rng(32 + 2)
+    rows = clustered(rng, 20000, 32, 2000, 0.5)
+    calls = [(-0.5, 12, 1000000, 777, 3)]
+    ref = single(engine, lambda e: e.load_rows(rows), calls)
+    trace = ref[0][0][0]
+    assert trace[-1] < trace[0]  # it merged
+    outs, results = run_group(2, lambda e: e.load_rows(rows), calls)
+    for r in range(2):
+        assert_same(outs[r], results[r], *ref)
+
+
+def test_sharded_hip_events_vs_single(engine):
+    """Option hip_events on every rank (event pairs around each projection): the same result, and
+    every projection launch timed."""
+    rng = np.random.default_rng(64 + 2)
+    rows = clustered(rng, 60000, 64, 1500, 0.05)
+    calls = [(0.8, 10, 1000000, 777, 3)]
+    ref = single(engine, lambda e: e.load_rows(rows), calls)
+
+    def load(e):
+        e.load_rows(rows)
+        e.set_option("hip_events", 1)
+
+    outs, results = run_group(2, load, calls)
+    for r in range(2):
+        assert_same(outs[r], results[r], *ref)
+        st = outs[r][0][2]
+        assert st["project_timed_launches"] == st["project_launches"] > 0
+
+
 @pytest.mark.parametrize("world,switch", [(2, 150000), (3, 120000), (4, 1 << 19)])
 def test_sharded_then_replicated_tail_vs_single(engine, world, switch):
     """The crossover: sharded while N_t >= switch, then every rank runs the rest on its replica."""

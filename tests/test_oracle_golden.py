@@ -18,6 +18,7 @@ from conftest import GOLDEN, golden
 
 sys.path.insert(0, GOLDEN)
 import kat_inputs  # noqa: E402
+import make_golden_thr  # noqa: E402
 
 C = np.uint32(2654435761)
 
@@ -68,8 +69,22 @@ def test_pcluster_matches_reference(oracle, name):
     assert np.array_equal(rows.view(np.uint32), z["out_rows"].view(np.uint32))
 
 
+@pytest.mark.parametrize("b,d", make_golden_thr.PCLUSTER_THR_SHAPES)
+def test_pcluster_threshold_domain_matches_reference(oracle, b, d):
+    """The merge test over the whole threshold domain (tests/golden/make_golden_thr.py): 0, below
+    0, tiny, at and one ulp either side of 1, +inf and NaN, on runs with copies, scaled and negated
+    copies, a zero row, an f64-orthogonalised pair and a pair with disjoint supports."""
+    rows, cases = make_golden_thr.load_pcluster_thr(b, d)
+    assert len(cases) == len(make_golden_thr.PCLUSTER_THR)
+    for thr, out_rows, out_off, out_ids in cases:
+        got_rows, off, ids = oracle.pcluster(rows, thr)
+        assert np.array_equal(off, out_off), thr
+        assert np.array_equal(ids, out_ids), thr
+        assert np.array_equal(got_rows.view(np.uint32), out_rows.view(np.uint32)), thr
+
+
 CLUSTER_CASES = ["cluster_d16", "cluster_d64", "cluster_d12", "cluster_d8_init", "cluster_nested",
-                 "cluster_nested_small"]
+                 "cluster_nested_small"] + sorted(make_golden_thr.CLUSTER_THR_CASES)
 
 
 @pytest.mark.parametrize("name", CLUSTER_CASES)
