@@ -244,6 +244,17 @@ int klsh_bucket_runs(klsh_ctx* ctx, const uint32_t* sorted_keys, uint64_t n, int
 /* p_cluster (reference function/cluster.cc:56-87) over the loaded rows taken as ONE bucket in
  * load order, at threshold thr.  Afterwards klsh_count/klsh_result give the survivors. */
 int klsh_pcluster(klsh_ctx* ctx, float thr);
+/* The per-slot state the engine keeps beside the rows and klsh_result never shows, for the live
+ * rows in klsh_result's order (read-only; on a context bound to a comm group, this rank's
+ * replica): nrm (n floats) = the cached sequential fp32 sum of squares that every later cosine
+ * test reads, cnt (n) = the member count that weighs every later consensus, image (n x d uint16)
+ * = the fp16 row image of the certified screens, filled only while option "fp16_image" reads 1.
+ * Computed on the host: *pad_nonzero = words of the live rows' zero pad (columns d .. d rounded
+ * up to 4) whose bits are not +0, *bad_links = live rows whose member chain, walked from its
+ * head, does not have exactly cnt nodes or does not end at the cached tail.  Any pointer may be
+ * NULL. */
+int klsh_row_state(klsh_ctx* ctx, float* nrm, uint32_t* cnt, uint16_t* image,
+                   uint64_t* pad_nonzero, uint64_t* bad_links);
 /* LSH::generateHashTable (reference hash/lshash.cc:36-42) under the seeding convention:
  * h hyperplanes of d floats starting at draw index *rng_counter (advanced by h). */
 int klsh_hyperplanes(uint32_t seed_base, uint64_t* rng_counter, int h, int d, float* table);

@@ -36,7 +36,7 @@ EXPORTED = (
     "klsh_comm_info", "klsh_set_option", "klsh_get_option", "klsh_wrs", "klsh_ttest2", "klsh_fastq_open",
     "klsh_fastq_next", "klsh_fastq_close", "klsh_kset_create", "klsh_kset_destroy",
     "klsh_check_reads", "klsh_extract_fastq", "klsh_build_khtable", "klsh_cuckoo_order",
-    "klsh_kmc_info", "klsh_bucket_runs",
+    "klsh_kmc_info", "klsh_bucket_runs", "klsh_row_state",
 )
 
 
@@ -170,6 +170,7 @@ def load_library() -> ctypes.CDLL:
                                           ctypes.c_int, _P]),
         "klsh_bucket_sort": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int, _P, _P]),
         "klsh_pcluster": (ctypes.c_int, [_P, ctypes.c_float]),
+        "klsh_row_state": (ctypes.c_int, [_P, _P, _P, _P, _u64p, _u64p]),
         "klsh_bucket_runs": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int, _u64p, _P, _P,
                                             _P]),
         "klsh_hyperplanes": (ctypes.c_int, [ctypes.c_uint32, _u64p, ctypes.c_int,
@@ -539,3 +540,18 @@ class Engine:
         _check(self._lib.klsh_result(self._ctx, _ptr(rows), _ptr(off), _ptr(ids)),
                "klsh_result")
         return rows, off, ids
+
+    def row_state(self) -> dict:
+        """The cached per-slot state of the live rows, in result() order (``klsh_row_state``):
+        nrm (n,) float32, cnt (n,) uint32, image (n, d) uint16 fp16 bits or None when no image is
+        kept, and the host-computed counters pad_nonzero and bad_links."""
+        n, _ = self.count()
+        nrm = np.zeros(n, dtype=np.float32)
+        cnt = np.zeros(n, dtype=np.uint32)
+        image = np.zeros((n, self.d), dtype=np.uint16) if self.get_option("fp16_image") else None
+        pad = ctypes.c_uint64(0)
+        bad = ctypes.c_uint64(0)
+        _check(self._lib.klsh_row_state(self._ctx, _ptr(nrm), _ptr(cnt), _ptr(image),
+                                        ctypes.byref(pad), ctypes.byref(bad)), "klsh_row_state")
+        return {"nrm": nrm, "cnt": cnt, "image": image, "pad_nonzero": pad.value,
+                "bad_links": bad.value}

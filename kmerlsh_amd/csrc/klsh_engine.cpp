@@ -2131,6 +2131,70 @@ int klsh_result(klsh_ctx* ctx, float* rows, uint64_t* member_offsets, uint64_t* 
   return 0;
 }
 
+// The per-slot state klsh_result does not show, for the live rows in its order: plain copies of
+// the device arrays and a host gather (read-only; on a context of a comm group, this rank's
+// replica).
+int klsh_row_state(klsh_ctx* ctx, float* nrm, uint32_t* cnt, uint16_t* image,
+                   uint64_t* pad_nonzero, uint64_t* bad_links) {
+  if (!ctx) return fail(KLSH_E_ARG, "null ctx");
+  if (!ctx->loaded) return fail(KLSH_E_STATE, "nothing loaded");
+  KLSH_HIP(hipSetDevice(ctx->device));
+  KLSH_HIP(hipStreamSynchronize(ctx->stream));  // (a load's image build may still be in flight)
+  const uint64_t n = ctx->n_live, S = ctx->slots, M = ctx->members;
+  const int d = ctx->d, dp = ctx->dp;
+  std::vector<uint32_t> ord(n);
+  if (n) KLSH_HIP(hipMemcpy(ord.data(), ctx->order, 4 * n, hipMemcpyDeviceToHost));
+  for (uint32_t sl : ord)
+    if (sl >= S) return fail(KLSH_E_STATE, "corrupt live order");
+  if (nrm && n) {
+    std::vector<float> a(S);
+    KLSH_HIP(hipMemcpy(a.data(), ctx->rows.nrm, 4 * S, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; ++i) nrm[i] = a[ord[i]];
+  }
+  std::vector<uint32_t> c(S);
+  if (S) KLSH_HIP(hipMemcpy(c.data(), ctx->rows.cnt, 4 * S, hipMemcpyDeviceToHost));
+  if (cnt)
+    for (uint64_t i = 0; i < n; ++i) cnt[i] = c[ord[i]];
+  if (image && n && ctx->rows.xh) {
+    std::vector<uint16_t> a(S * (uint64_t)dp);
+    KLSH_HIP(hipMemcpy(a.data(), ctx->rows.xh, 2 * a.size(), hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; ++i)
+      memcpy(image + i * d, a.data() + (uint64_t)ord[i] * dp, 2 * (size_t)d);
+  }
+  if (pad_nonzero) {
+    uint64_t bad = 0;
+    if (n && dp > d) {
+      std::vector<uint32_t> a(S * (uint64_t)dp);
+      KLSH_HIP(hipMemcpy(a.data(), ctx->rows.x, 4 * a.size(), hipMemcpyDeviceToHost));
+      for (uint64_t i = 0; i < n; ++i)
+        for (int k = d; k < dp; ++k) bad += a[(uint64_t)ord[i] * dp + k] != 0u;
+    }
+    *pad_nonzero = bad;
+  }
+  if (bad_links) {
+    std::vector<uint32_t> head(S), tail(S), nxt(M);
+    if (S) {
+      KLSH_HIP(hipMemcpy(head.data(), ctx->rows.head, 4 * S, hipMemcpyDeviceToHost));
+      KLSH_HIP(hipMemcpy(tail.data(), ctx->rows.tail, 4 * S, hipMemcpyDeviceToHost));
+    }
+    if (M) KLSH_HIP(hipMemcpy(nxt.data(), ctx->rows.nxt, 4 * M, hipMemcpyDeviceToHost));
+    uint64_t bad = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+      // exactly cnt nodes from head, the last of them tail (an empty list: head == tail == nil)
+      const uint32_t want = c[ord[i]];
+      uint32_t node = head[ord[i]], last = klsh::kNil, len = 0;
+      while (node != klsh::kNil && node < M && len <= want) {
+        last = node;
+        node = nxt[node];
+        ++len;
+      }
+      bad += !(node == klsh::kNil && len == want && last == tail[ord[i]]);
+    }
+    *bad_links = bad;
+  }
+  return 0;
+}
+
 // The projection kernels the loop uses, on caller rows: the same dispatch (launch_project) with
 // the context's projection options, the fp16 row image built from the rows where the loop keeps
 // one (d = 16, 32, 64), so the certified screens and their exact fix-up paths are what a test of

@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, GOLDEN)
 import make_golden_thr  # noqa: E402
 from make_golden_thr import threshold_rows  # noqa: E402
+from row_state import options  # noqa: E402
 
 
 def same_bits(a, b):
@@ -400,24 +401,6 @@ def test_pcluster_huge_runs_folded_vs_oracle(engine, oracle, b, d, groups, noise
         engine.pcluster(thr)
         got = engine.result()
     assert_same_result(got, *oracle.pcluster(rows, thr))
-
-
-class options:
-    """Engine options set for a block and restored to their previous values after it."""
-
-    def __init__(self, engine, **kv):
-        self.engine, self.kv, self.old = engine, kv, {}
-
-    def __enter__(self):
-        for k, v in self.kv.items():
-            self.old[k] = self.engine.get_option(k)
-            self.engine.set_option(k, v)
-        return self.engine
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            self.engine.set_option(k, v)
-        return False
 
 
 @pytest.mark.parametrize("d,screen", [(64, 1), (32, 1), (64, 0)])
