@@ -326,7 +326,9 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* set, const char* in_path,
  * out_dir NULL or "" = the current directory.  stats may be NULL. */
 typedef struct klsh_khtable_stats {
   uint64_t struct_size; /* in: sizeof(klsh_khtable_stats) */
-  uint64_t kmap_size, records, records_listed;
+  uint64_t kmap_size;
+  uint64_t records;        /* records streamed: both passes read every database, so twice their sum */
+  uint64_t records_listed; /* records inside [min_count, max_count], each counted once */
   double io_ms;     /* host reads of the .kmc_suf streams */
   double total_ms;
   double order_ms;  /* host replay of the reference's libcuckoo inserts (the row order) */
@@ -339,6 +341,23 @@ int klsh_cuckoo_order(const uint64_t* images, uint64_t n, int k, uint32_t* order
 /* The host parse of a KMC database's prefix file (<name>.kmc_pre: version, header, prefix LUT) as
  * klsh_build_khtable does it, every file-derived offset checked (a test hook).  Host only. */
 int klsh_kmc_info(const char* name, int* k, uint64_t* total, uint64_t* lut_entries);
+/* Test hooks of klsh_build_khtable, context options (klsh_set_option / klsh_get_option; the
+ * defaults are the product's behaviour and cost nothing):
+ *   "kmc_chunk_records"   N > 0: the .kmc_suf streams are read N records at a time, not the 64 MB
+ *                         of records a production chunk holds (never more than that; 0 = default),
+ *                         so a small database takes the many-chunk path
+ *   "kmc_ordinal_base"    the first-appearance ordinal of sample 0's first record (default 0, at
+ *                         most 2^48): from 2^32 - records on, the ordinals need their high words
+ *   "kmc_keep_first"      1 = a call keeps its first-appearance list for klsh_khtable_first
+ *   read-only, of the context's last call: "kmc_decode_launches" (record-decode launches of the
+ *   union pass: one per chunk per sample) and "kmc_high_sort" (1 = the second sort, on the
+ *   ordinals' high words, ran).
+ * klsh_khtable_first: the distinct canonical k-mers of the last call made with "kmc_keep_first"
+ * on, in the order of their first ordinal (sample, then record; the all-A k-mer a filtered sample
+ * adds comes after that sample's records) — what the libcuckoo replay is fed, before the row
+ * order hides most of it.  *n: in, the capacity of images; out, the count (images NULL: only the
+ * count; KLSH_E_RANGE if the capacity is too small). */
+int klsh_khtable_first(klsh_ctx* ctx, uint64_t* images, uint64_t* n);
 int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, int n_samples, int k,
                        const char* out_dir, klsh_khtable_stats* stats);
 

@@ -36,7 +36,7 @@ EXPORTED = (
     "klsh_comm_info", "klsh_set_option", "klsh_get_option", "klsh_wrs", "klsh_ttest2", "klsh_fastq_open",
     "klsh_fastq_next", "klsh_fastq_close", "klsh_kset_create", "klsh_kset_destroy",
     "klsh_check_reads", "klsh_extract_fastq", "klsh_build_khtable", "klsh_cuckoo_order",
-    "klsh_kmc_info", "klsh_bucket_runs", "klsh_row_state",
+    "klsh_kmc_info", "klsh_khtable_first", "klsh_bucket_runs", "klsh_row_state",
 )
 
 
@@ -201,6 +201,7 @@ def load_library() -> ctypes.CDLL:
                                               ctypes.c_int, ctypes.c_char_p, _P]),
         "klsh_cuckoo_order": (ctypes.c_int, [_P, ctypes.c_uint64, ctypes.c_int, _P]),
         "klsh_kmc_info": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), _u64p, _u64p]),
+        "klsh_khtable_first": (ctypes.c_int, [_P, _P, _u64p]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("KLSH_LIB") and not hasattr(lib, name):
@@ -267,6 +268,17 @@ def cuckoo_order(images: np.ndarray, k: int) -> tuple[np.ndarray, int]:
     if hp < 0:
         _check(hp, "klsh_cuckoo_order")
     return out, int(hp)
+
+
+def kmc_info(name: str) -> tuple[int, int, int]:
+    """The host parse of <name>.kmc_pre (no GPU needed): (k, total records, LUT entries)."""
+    lib = load_library()
+    k = ctypes.c_int(0)
+    total = ctypes.c_uint64(0)
+    lut = ctypes.c_uint64(0)
+    _check(lib.klsh_kmc_info(name.encode(), ctypes.byref(k), ctypes.byref(total), ctypes.byref(lut)),
+           "klsh_kmc_info")
+    return k.value, total.value, lut.value
 
 
 def synth_counts(n: int, d: int, seed: int, genomes: int = 0, threads: int = 0):
@@ -478,6 +490,16 @@ class Engine:
         _check(self._lib.klsh_build_khtable(self._ctx, arr, len(kmc_names), k, out_dir.encode(),
                                             ctypes.byref(st)), "klsh_build_khtable")
         return st.as_dict()
+
+    def khtable_first(self) -> np.ndarray:
+        """The first-appearance list of the last build_khtable made with option "kmc_keep_first"
+        on (a test hook): distinct canonical k-mer images by first (sample, record) ordinal."""
+        n = ctypes.c_uint64(0)
+        _check(self._lib.klsh_khtable_first(self._ctx, None, ctypes.byref(n)), "klsh_khtable_first")
+        out = np.zeros(n.value, np.uint64)
+        _check(self._lib.klsh_khtable_first(self._ctx, _ptr(out), ctypes.byref(n)),
+               "klsh_khtable_first")
+        return out
 
     def pcluster(self, thr: float) -> None:
         _check(self._lib.klsh_pcluster(self._ctx, ctypes.c_float(thr)), "klsh_pcluster")

@@ -213,6 +213,8 @@ struct klsh_ctx {
   // the (row, hyperplane) pairs its screen left to the exact chains
   int last_hash_kernel = klsh::kPkNone;
   uint64_t last_hash_close = 0;
+  // klsh_build_khtable's test hooks and reach counters (klsh_kmc.cpp)
+  klsh::KmcHooks kmc;
 
   ~klsh_ctx() { release(); }
 
@@ -763,6 +765,7 @@ static int collect_kernel_times(klsh_ctx* ctx, int last_set, klsh_stats* st) {
 namespace klsh {
 int ctx_device(const klsh_ctx* ctx) { return ctx->device; }
 hipStream_t ctx_stream(const klsh_ctx* ctx) { return ctx->stream; }
+KmcHooks& ctx_kmc(klsh_ctx* ctx) { return ctx->kmc; }
 int set_error(int code, const char* msg) { return fail(code, msg); }
 }  // namespace klsh
 
@@ -1985,6 +1988,20 @@ int klsh_set_option(klsh_ctx* ctx, const char* name, int64_t value) {
     if (ctx->comm) ctx->comm->timeout_s = (double)value;
     return 0;
   }
+  if (n == "kmc_chunk_records") {
+    if (value < 0) return fail(KLSH_E_ARG, "kmc_chunk_records must be >= 0");
+    ctx->kmc.chunk_records = (uint64_t)value;
+    return 0;
+  }
+  if (n == "kmc_ordinal_base") {
+    if (value < 0 || value > (1ll << 48)) return fail(KLSH_E_ARG, "kmc_ordinal_base must be in [0, 2^48]");
+    ctx->kmc.ordinal_base = (uint64_t)value;
+    return 0;
+  }
+  if (n == "kmc_keep_first") {
+    if (!value) std::vector<uint64_t>().swap(ctx->kmc.first);
+    return flag(&ctx->kmc.keep_first);
+  }
   if (n == "h16_grid") return grid(&ctx->pw.h16_grid);
   if (n == "h16_segcap") return grid(&ctx->pw.segcap);
   if (n == "wide_grid") return grid(&ctx->pw.wide_grid);
@@ -2041,6 +2058,11 @@ int klsh_get_option(klsh_ctx* ctx, const char* name, int64_t* value) {
   else if (n == "progress") *value = ctx->progress;
   else if (n == "projection") *value = ctx->pw.variant;
   else if (n == "comm_timeout_s") *value = (int64_t)ctx->comm_timeout_s;
+  else if (n == "kmc_chunk_records") *value = (int64_t)ctx->kmc.chunk_records;
+  else if (n == "kmc_ordinal_base") *value = (int64_t)ctx->kmc.ordinal_base;
+  else if (n == "kmc_keep_first") *value = ctx->kmc.keep_first;
+  else if (n == "kmc_decode_launches") *value = (int64_t)ctx->kmc.decode_launches;
+  else if (n == "kmc_high_sort") *value = ctx->kmc.high_sort;
   else if (n == "h16_grid") *value = ctx->pw.h16_grid;
   else if (n == "h16_segcap") *value = ctx->pw.segcap;
   else if (n == "wide_grid") *value = ctx->pw.wide_grid;

@@ -7,6 +7,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <vector>
+
 #include "klsh.h"
 
 namespace klsh {
@@ -464,9 +466,22 @@ void launch_kmc_emit_keys(const uint64_t* tab, const uint32_t* order, uint64_t n
 void launch_kmc_emit(const uint32_t* acc, const uint32_t* order, uint64_t n, uint16_t* out,
                      hipStream_t s);
 
-// The engine's context, for the other host translation units (klsh_extract.cpp).
+// klsh_build_khtable's test hooks and what its last call on the context reached (options
+// "kmc_chunk_records", "kmc_ordinal_base", "kmc_keep_first"; read-only "kmc_decode_launches",
+// "kmc_high_sort"; klsh_khtable_first).  The defaults are the product's behaviour.
+struct KmcHooks {
+  uint64_t chunk_records = 0;    // records per .kmc_suf chunk (0 = what 64 MB hold; never more)
+  uint64_t ordinal_base = 0;     // ordinal of sample 0's record 0
+  bool keep_first = false;       // keep the first-appearance list of the next calls in `first`
+  uint64_t decode_launches = 0;  // pass 1's k_kmc_decode launches
+  int high_sort = 0;             // 1 = the ordinals' high words were sorted
+  std::vector<uint64_t> first;   // distinct canonical k-mers by first ordinal
+};
+
+// The engine's context, for the other host translation units (klsh_extract.cpp, klsh_kmc.cpp).
 int ctx_device(const klsh_ctx* ctx);
 hipStream_t ctx_stream(const klsh_ctx* ctx);
+KmcHooks& ctx_kmc(klsh_ctx* ctx);
 int set_error(int code, const char* msg);  // sets klsh_last_error(), returns code
 
 }  // namespace klsh

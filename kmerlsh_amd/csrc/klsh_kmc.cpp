@@ -327,6 +327,19 @@ extern "C" int klsh_cuckoo_order(const uint64_t* images, uint64_t n, int k, uint
   return t.hashpower();
 }
 
+// Test hook (tests/test_mode_b.py): the distinct canonical k-mers of the context's last
+// klsh_build_khtable call in the order of their first ordinal, what CuckooOrder then replays.
+extern "C" int klsh_khtable_first(klsh_ctx* ctx, uint64_t* images, uint64_t* n) {
+  if (!ctx || !n) return set_error(KLSH_E_ARG, "null argument");
+  const std::vector<uint64_t>& first = klsh::ctx_kmc(ctx).first;
+  const uint64_t room = *n;
+  *n = first.size();
+  if (!images) return KLSH_OK;
+  if (room < first.size()) return set_error(KLSH_E_RANGE, "klsh_khtable_first: output too small");
+  if (!first.empty()) memcpy(images, first.data(), first.size() * 8);
+  return KLSH_OK;
+}
+
 #define KLSH_KHIP(call)                                                                   \
   do {                                                                                    \
     hipError_t e_ = (call);                                                               \
@@ -345,6 +358,10 @@ extern "C" int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, i
     return set_error(KLSH_E_ARG, "klsh_khtable_stats.struct_size != sizeof: built against another klsh.h");
   klsh_khtable_stats local{};
   local.struct_size = sizeof(local);
+  klsh::KmcHooks& hooks = klsh::ctx_kmc(ctx);  // test hooks; what this call reaches
+  hooks.decode_launches = 0;
+  hooks.high_sort = 0;
+  hooks.first.clear();
   std::vector<KmcDb> dbs(n_samples);
   uint64_t records = 0;
   for (int j = 0; j < n_samples; ++j) {
@@ -370,8 +387,7 @@ extern "C" int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, i
   uint16_t* col = nullptr;
   uint8_t* drec = nullptr;
   std::vector<uint8_t> hrec(kChunkBytes);
-  std::vector<uint32_t> order_dbg;
-  std::vector<uint64_t> base(n_samples + 1, 0);
+  std::vector<uint64_t> base(n_samples + 1, hooks.ordinal_base);  // base[j]: sample j's first ordinal
   uint32_t kmap = 0;
   FILE *fh = nullptr, *fb = nullptr, *fl = nullptr;
   std::vector<float> coverage(n_samples, 0.0f);
@@ -410,7 +426,8 @@ extern "C" int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, i
         rc = set_error(KLSH_E_ARG, (db.suf + ": bad marker").c_str());
         goto done;
       }
-      const uint64_t per_chunk = kChunkBytes / kp.rec_size;
+      uint64_t per_chunk = kChunkBytes / kp.rec_size;  // what hrec / drec / drep / dcnt hold
+      if (hooks.chunk_records) per_chunk = std::min<uint64_t>(per_chunk, hooks.chunk_records);
       float cov = 0.0f;
       for (uint64_t r0 = 0; r0 < db.total; r0 += per_chunk) {
         const uint64_t n = std::min<uint64_t>(per_chunk, db.total - r0);
@@ -423,6 +440,7 @@ extern "C" int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, i
         local.io_ms += now_ms() - tio;
         KLSH_KHIP(hipMemcpyAsync(drec, hrec.data(), n * kp.rec_size, hipMemcpyHostToDevice, s));
         klsh::launch_kmc_decode(drec, n, r0, kp, dlut, db.lut.size(), drep, dcnt, nvalid, s);
+        if (pass == 0) ++hooks.decode_launches;
         if (pass == 0) klsh::launch_kmc_union(drep, n, base[j] + r0, tab, first, mask, s);
         else klsh::launch_kmc_count(drep, dcnt, n, tab, mask, acc, s);
         KLSH_KHIP(hipGetLastError());
@@ -484,6 +502,7 @@ extern "C" int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, i
       int hbits = 0;
       while (hbits < 32 && (last >> 32) >> hbits) ++hbits;
       if (hbits) {
+        hooks.high_sort = 1;
         uint32_t* hk = ok_ == lo ? lo2 : lo;  // the free key buffer
         uint32_t* hv = ov_ == slots ? slots2 : slots;
         klsh::launch_kmc_hi(first, ov_, kmap, hk, s);
@@ -504,6 +523,7 @@ extern "C" int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, i
         KLSH_KHIP(hipMemcpyAsync(hslots.data(), slots, kmap * 4ull, hipMemcpyDeviceToHost, s));
       }
       KLSH_KHIP(hipStreamSynchronize(s));
+      if (hooks.keep_first) hooks.first = hkeys;
       {  // the reference's row order: its libcuckoo table after the first-appearance inserts
         const double tc = now_ms();
         std::vector<uint64_t> hv(kmap);

@@ -5,7 +5,8 @@ Writes .kmc_pre / .kmc_suf pairs in the two layouts the reference's vendored KMC
 KMC2/3 (version 0x200: per-signature-bin LUTs + signature map + packed header).  A record is the
 k-mer's suffix after the lut_prefix_length-symbol prefix, big-endian 2-bit symbols, then a
 little-endian counter of counter_size bytes.  `write_case(dir, case)` also writes a.txt/b.txt
-("<fastq> <kmc db name>" lines) for the reference CLI's mode B (`-M B --only`).
+("<fastq> <kmc db name>" lines) for the reference CLI's mode B (`-M B --only`);
+`write_edge_case(dir, case)` does the same for EDGE_CASES, the record layouts at the format's edges.
 The databases are drawn from a splitmix64 stream: byte-reproducible anywhere.
 """
 from __future__ import annotations
@@ -128,8 +129,92 @@ def write_case(dirpath: str, case: str) -> dict:
 
 
 def cli_args(case: str) -> list:
-    return ["-a", "a.txt", "-b", "b.txt", "-o", "A", "-p", "B", "-K", str(CASES[case]["k"]), "-M", "B",
+    k = (CASES.get(case) or EDGE_CASES[case])["k"]
+    return ["-a", "a.txt", "-b", "b.txt", "-o", "A", "-p", "B", "-K", str(k), "-M", "B",
             "--only", "--verbose", "-T", "1"]
+
+
+# Record layouts at the edges of what the listing accepts: p = 0, k = p (a record is its counter
+# alone), 3-byte counters, k below 5 (one Kmer byte, palindromes), k = 32 with p = 0, KMC2 with
+# p = 0 (one LUT entry per bin), a [min_count, max_count] window that filters at both ends, a
+# sample with every record filtered, an empty sample.  counts: (low, high) drawn uniformly;
+# big: one record in three is drawn from this range instead.  extra: k-mers every sample lists.
+EDGE_CASES = {
+    "e_k4p0": dict(k=4, version=0, p=0, counter_size=1, bins=1, n1=2, n2=1, seed=211,
+                   min_count=1, max_count=255, counts=(1, 255)),
+    "e_k4p4": dict(k=4, version=0, p=4, counter_size=2, bins=1, n1=2, n2=2, seed=223,
+                   min_count=1, max_count=65535, counts=(1, 2000), big=(30000, 65535)),
+    "e_k1p1": dict(k=1, version=0, p=1, counter_size=1, bins=1, n1=2, n2=2, seed=227,
+                   min_count=1, max_count=255, counts=(1, 255)),
+    "e_k5p1": dict(k=5, version=0x200, p=1, counter_size=3, bins=3, n1=2, n2=2, seed=229,
+                   min_count=1, max_count=(1 << 24) - 1, counts=(1, 3000), big=(50000, (1 << 24) - 1)),
+    "e_k9p9": dict(k=9, version=0, p=9, counter_size=4, bins=1, n1=2, n2=2, seed=233, pool=1500,
+                   min_count=2, max_count=0xFFFFFFFF, counts=(1, 6), big=(60000, 0xFFFFFFFF),
+                   # the two strands of one k-mer whose 32-bit sum wraps to 1: 65535 when clamped
+                   extra=[("ACGTTGCAA", 0xFFFFFFFF), ("TTGCAACGT", 2)]),
+    "e_k13win": dict(k=13, version=0, p=5, counter_size=2, bins=1, n1=2, n2=2, seed=239, pool=1500,
+                     min_count=20, max_count=200, counts=(1, 300)),
+    "e_k12win2": dict(k=12, version=0x200, p=4, counter_size=1, bins=3, n1=2, n2=2, seed=241,
+                      pool=1500, min_count=30, max_count=220, counts=(1, 255),
+                      extra=[("A" * 12, 100), ("T" * 12, 60)]),
+    "e_k8p0v2": dict(k=8, version=0x200, p=0, counter_size=2, bins=3, n1=2, n2=2, seed=251,
+                     pool=1200, min_count=1, max_count=65535, counts=(1, 65535)),
+    "e_k32p0": dict(k=32, version=0, p=0, counter_size=2, bins=1, n1=2, n2=2, seed=257, pool=1500,
+                    min_count=1, max_count=65535, counts=(1, 65535),
+                    extra=[("A" * 32, 7), ("T" * 32, 11), ("AC" * 16, 13), ("ACGT" * 8, 17)]),
+    "e_allfilt": dict(k=21, version=0, p=9, counter_size=1, bins=1, n1=1, n2=1, seed=263, pool=800,
+                      min_count=10, max_count=255, counts=(1, 9)),
+    "e_empty": dict(k=21, version=0, p=9, counter_size=1, bins=1, n1=2, n2=2, seed=269, pool=1200,
+                    min_count=1, max_count=255, counts=(1, 255), empty=(0,)),
+}
+
+
+def write_edge_case(dirpath: str, case: str) -> dict:
+    """Below k = 7 a sample lists a random three quarters of all 4^k k-mers as they are (both
+    strands of most); above, two thirds of a pool shared by the samples, either strand at random
+    and both for one in five."""
+    c = EDGE_CASES[case]
+    k = c["k"]
+    rng = SplitMix(c["seed"])
+    if k < 7:
+        pool = ["".join("ACGT"[(v >> (2 * (k - 1 - i))) & 3] for i in range(k)) for v in range(4 ** k)]
+    else:
+        pool = ["".join("ACGT"[rng.below(4)] for _ in range(k)) for _ in range(c["pool"])]
+
+    def count():
+        lo, hi = c["big"] if "big" in c and rng.below(3) == 0 else c["counts"]
+        return lo + rng.below(hi - lo + 1)
+
+    d = c["n1"] + c["n2"]
+    names = []
+    for j in range(d):
+        recs = {}
+        if j not in c.get("empty", ()):
+            if k < 7:
+                keys = [(rng.next(), s) for s in pool]
+                for _, s in sorted(keys)[:max(1, len(pool) * 3 // 4)]:
+                    recs[s] = count()
+            else:
+                for s in pool:
+                    if rng.below(3) == 0:
+                        continue
+                    r = rng.below(5)
+                    if r == 0:
+                        recs[s] = count()
+                        recs[revcomp(s)] = count()
+                    else:
+                        recs[revcomp(s) if r & 1 else s] = count()
+            for s, cnt in c.get("extra", ()):
+                recs[s] = cnt
+        name = "db%d" % j
+        write_db(os.path.join(dirpath, name), k, sorted(recs.items()), c["version"], c["p"],
+                 c["counter_size"], c["min_count"], c["max_count"], bins=c["bins"])
+        names.append(name)
+    with open(os.path.join(dirpath, "a.txt"), "w") as f:
+        f.write("".join("s%d.fq %s\n" % (j, names[j]) for j in range(c["n1"])))
+    with open(os.path.join(dirpath, "b.txt"), "w") as f:
+        f.write("".join("s%d.fq %s\n" % (j, names[j]) for j in range(c["n1"], d)))
+    return dict(c, d=d, names=names)
 
 
 # Large mode-B cases (the reference's libcuckoo table under load): KMC1 databases of random

@@ -56,10 +56,11 @@ def test_fastq_reader_sanitized(driver, tmp_path):
 
 def test_kmc_prefix_parse_sanitized(driver, tmp_path):
     names = []
-    for case in sorted(kmc_inputs.CASES):
+    for case in sorted(kmc_inputs.CASES) + sorted(kmc_inputs.EDGE_CASES):
         d = tmp_path / case
         d.mkdir()
-        info = kmc_inputs.write_case(str(d), case)
+        info = (kmc_inputs.write_case if case in kmc_inputs.CASES
+                else kmc_inputs.write_edge_case)(str(d), case)
         names += [str(d / nm) for nm in info["names"]]
     out = run([driver, "kmc"] + names)
     assert "kmc ok" in out
