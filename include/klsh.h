@@ -361,6 +361,47 @@ int klsh_khtable_first(klsh_ctx* ctx, uint64_t* images, uint64_t* n);
 int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, int n_samples, int k,
                        const char* out_dir, klsh_khtable_stats* stats);
 
+/* ---- mode K: the k-mer table from FASTQ files (reference io/ioHT.cc:83-199, kmc = true) ------- */
+/* What the reference gets from `kmc -k<K> -r -cs65535 -ci<count_min>` per sample followed by
+ * buildKHtable on those databases, without the external counter and without writing databases.
+ * Per sample (one FASTQ file, gzip or plain, read once with klsh_fastq_next; only the sequences
+ * are used): A C G T a c g t are bases, any other character breaks the read (no k-mer spans it);
+ * every window of k bases is one occurrence of its canonical k-mer, the smaller of the window and
+ * its reverse complement as KMC values (base 0 most significant, A < C < G < T); a k-mer is listed
+ * with min(occurrences, 65535) when occurrences >= count_min (count_min < 1 is taken as 1).  The
+ * listing order is ascending KMC value, the order of a KMC1-layout database (a convention: KMC3's
+ * own bin-by-bin listing depends on statistics of its input; only the row order of
+ * the files depends on it).  The listings then go through the table build of
+ * klsh_build_khtable unchanged: kmer_set.hex, kmer_count.bin and kmer_count.log in out_dir.
+ * k in [1, 32].  stats may be NULL. */
+typedef struct klsh_kcount_stats {
+  uint64_t struct_size; /* in: sizeof(klsh_kcount_stats) */
+  uint64_t kmap_size, reads, bases, positions /* valid k-mer windows */,
+      distinct /* sum over samples, before count_min */, listed /* after */, batches, rehashes;
+  double kernel_ms; /* HIP-event time of the counting kernels */
+  double parse_ms;  /* host FASTQ parsing (gzip included) */
+  double order_ms;  /* host replay of the reference's libcuckoo inserts (the row order) */
+  double total_ms;
+} klsh_kcount_stats;
+int klsh_count_khtable(klsh_ctx* ctx, const char* const* fastq_paths, int n_samples, int k,
+                       int count_min, const char* out_dir, klsh_kcount_stats* stats);
+/* Test hooks of klsh_count_khtable, context options (the defaults are the product's behaviour and
+ * cost nothing):
+ *   "kcount_batch_reads"   N > 0: N reads per batch (0 = default, 2^18)
+ *   "kcount_table_slots"   a sample's initial table: a power of two >= 1024 (0 = default, 2^22);
+ *                          the table doubles between batches when the next batch could load it
+ *                          past one half
+ *   "kcount_keep_listing"  1 = a call keeps its per-sample listings for klsh_kcount_listing
+ *   read-only, of the context's last call: "kcount_batches", "kcount_rehashes",
+ *   "kcount_peak_slots" (the largest sample table); and "kcount_window", the k-mer positions per
+ *   LDS window of the counting kernel.
+ * "kmc_keep_first" / klsh_khtable_first work after klsh_count_khtable as after a build.
+ * klsh_kcount_listing: sample `sample`'s listing of the last call made with
+ * "kcount_keep_listing" on: KMC values ascending and their counts.  *n: in, the capacity of the
+ * outputs; out, the count (both outputs NULL: only the count; KLSH_E_RANGE if too small). */
+int klsh_kcount_listing(klsh_ctx* ctx, int sample, uint64_t* kmc_values, uint32_t* counts,
+                        uint64_t* n);
+
 /* ---- synthetic workload (klsh-synth v1) ------------------------------------ */
 /* Host-side, deterministic on any machine (integer hashing + glibc exp/log/sqrt): fills counts
  * (sample-major d x n uint16, the kmer_count.bin layout) and coverage[d] = sum over i of ln(c)

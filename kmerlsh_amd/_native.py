@@ -37,6 +37,7 @@ EXPORTED = (
     "klsh_fastq_next", "klsh_fastq_close", "klsh_kset_create", "klsh_kset_destroy",
     "klsh_check_reads", "klsh_extract_fastq", "klsh_build_khtable", "klsh_cuckoo_order",
     "klsh_kmc_info", "klsh_khtable_first", "klsh_bucket_runs", "klsh_row_state",
+    "klsh_count_khtable", "klsh_kcount_listing",
 )
 
 
@@ -114,6 +115,24 @@ class KlshExtractStats(_Sized):
         ("abnormal", ctypes.c_uint64),
         ("kernel_ms", ctypes.c_double),
         ("parse_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+    ]
+
+
+class KlshKcountStats(_Sized):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("kmap_size", ctypes.c_uint64),
+        ("reads", ctypes.c_uint64),
+        ("bases", ctypes.c_uint64),
+        ("positions", ctypes.c_uint64),
+        ("distinct", ctypes.c_uint64),
+        ("listed", ctypes.c_uint64),
+        ("batches", ctypes.c_uint64),
+        ("rehashes", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+        ("parse_ms", ctypes.c_double),
+        ("order_ms", ctypes.c_double),
         ("total_ms", ctypes.c_double),
     ]
 
@@ -202,6 +221,9 @@ def load_library() -> ctypes.CDLL:
         "klsh_cuckoo_order": (ctypes.c_int, [_P, ctypes.c_uint64, ctypes.c_int, _P]),
         "klsh_kmc_info": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), _u64p, _u64p]),
         "klsh_khtable_first": (ctypes.c_int, [_P, _P, _u64p]),
+        "klsh_count_khtable": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_char_p, _P]),
+        "klsh_kcount_listing": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, _u64p]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("KLSH_LIB") and not hasattr(lib, name):
@@ -490,6 +512,27 @@ class Engine:
         _check(self._lib.klsh_build_khtable(self._ctx, arr, len(kmc_names), k, out_dir.encode(),
                                             ctypes.byref(st)), "klsh_build_khtable")
         return st.as_dict()
+
+    def count_khtable(self, fastq_paths, k: int, count_min: int = 2, out_dir: str = "") -> dict:
+        """Mode K: kmer_set.hex / kmer_count.bin / kmer_count.log from one FASTQ file per sample
+        (k-mers counted on the GPU, listed from count_min occurrences on)."""
+        arr = (ctypes.c_char_p * len(fastq_paths))(*[os.fspath(n).encode() for n in fastq_paths])
+        st = KlshKcountStats()
+        _check(self._lib.klsh_count_khtable(self._ctx, arr, len(fastq_paths), k, count_min,
+                                            os.fspath(out_dir).encode(), ctypes.byref(st)),
+               "klsh_count_khtable")
+        return st.as_dict()
+
+    def kcount_listing(self, sample: int) -> tuple[np.ndarray, np.ndarray]:
+        """Sample `sample`'s listing of the last count_khtable made with option
+        "kcount_keep_listing" on (a test hook): (KMC values ascending, counts)."""
+        n = ctypes.c_uint64(0)
+        _check(self._lib.klsh_kcount_listing(self._ctx, sample, None, None, ctypes.byref(n)),
+               "klsh_kcount_listing")
+        vals, cnts = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint32)
+        _check(self._lib.klsh_kcount_listing(self._ctx, sample, _ptr(vals), _ptr(cnts),
+                                             ctypes.byref(n)), "klsh_kcount_listing")
+        return vals, cnts
 
     def khtable_first(self) -> np.ndarray:
         """The first-appearance list of the last build_khtable made with option "kmc_keep_first"

@@ -1,4 +1,4 @@
-// kmerLSH-compatible command line (modes C and E) over the gfx950 engine.
+// kmerLSH-compatible command line (modes K, B, C and E) over the gfx950 engine.
 //
 // Same flags and files as the reference (app/kmerLSH.cc:147-276, :432-580), run in the directory
 // holding kmer_count.bin / kmer_count.log, with -a/-b sample lists ("<fastq> <kmc name>" lines):
@@ -10,12 +10,17 @@
 //           whose k-mer vote passes -V (IOFQ::Extracting, io/ioFastQ.cc:161-195).
 //   mode B  reads the KMC databases named in the lists' second column and writes kmer_set.hex,
 //           kmer_count.bin, kmer_count.log (io/ioHT.cc:83-199 with existing databases).
+//   mode K  counts the k-mers of the FASTQ files named in the lists' first column on the GPU (what
+//           the reference runs `kmc -k<K> -r -cs65535 -ci<C>` for, io/ioHT.cc:100-103) and writes
+//           the same three files; no KMC database is written and the second column is unused.
 // Mode selection as the reference's (app/kmerLSH.cc:234-275): -M E [--only] extracts only,
 // -M C --only clusters only, -M C clusters and then extracts, -M B --only builds the table only,
-// -M B builds, clusters and extracts; mode K (running the KMC counter itself) is not part of
-// this engine.
-//   kmerLSH -a A.txt -b B.txt [-o A -p B] [-I iters] [-N min_sim] [-K k] [-S size] [-P pval]
-//           [-V vote] [-F file] [-M C|E] [--only] [--verbose] [--seed S] [--device D]
+// -M B builds, clusters and extracts, -M K --only counts and writes the table only, -M K or no -M
+// (the reference's default: everything) counts, clusters and extracts.
+//   kmerLSH -a A.txt -b B.txt [-o A -p B] [-I iters] [-N min_sim] [-K k] [-C count_min] [-S size]
+//           [-P pval] [-V vote] [-F file] [-M K|B|C|E] [--only] [--verbose] [--seed S] [--device D]
+// -C is the smallest count a k-mer is listed with (kmc's -ci, default 2); -X is accepted and
+// ignored (kmc's memory limit).
 // Additions: --seed (the reference seeds from std::random_device; SURVEY.md §8(c) convention)
 // and --device.  -T is accepted and ignored (results never depend on a thread count).
 // The init pass keeps the reference's 1e8-row batching and re-cluster passes
@@ -160,6 +165,27 @@ int run_build(klsh_ctx* ctx, const char* in1, const char* in2, int k, bool verbo
   return 0;
 }
 
+// Mode K (buildKHtable with kmc = true): the FASTQ files of the lists' first column counted on the
+// GPU -> kmer_set.hex / kmer_count.bin / kmer_count.log in the current directory.
+int run_count(klsh_ctx* ctx, const char* in1, const char* in2, int k, int count_min, bool verbose) {
+  std::vector<std::string> names = sample_paths(in1, 0), n2 = sample_paths(in2, 0);
+  names.insert(names.end(), n2.begin(), n2.end());
+  std::vector<const char*> ptrs;
+  for (const auto& n : names) ptrs.push_back(n.c_str());
+  klsh_kcount_stats st{};
+  st.struct_size = sizeof(st);
+  check(klsh_count_khtable(ctx, ptrs.data(), (int)ptrs.size(), k, count_min, "", &st),
+        "klsh_count_khtable");
+  if (verbose)
+    printf("k-mer table: %llu k-mers (%llu listed of %llu distinct, %llu k-mer positions, %llu reads "
+           "of %zu samples; %.1f ms, counting kernels %.1f ms, parsing %.1f ms, %llu rehashes)\n",
+           (unsigned long long)st.kmap_size, (unsigned long long)st.listed,
+           (unsigned long long)st.distinct, (unsigned long long)st.positions,
+           (unsigned long long)st.reads, names.size(), st.total_ms, st.kernel_ms, st.parse_ms,
+           (unsigned long long)st.rehashes);
+  return 0;
+}
+
 // Mode E (app/kmerLSH.cc:521-580).
 int run_extract(klsh_ctx* ctx, const std::vector<std::string>& s1,
                 const std::vector<std::string>& s2, const std::string& clust_file,
@@ -292,7 +318,8 @@ int run_extract(klsh_ctx* ctx, const std::vector<std::string>& s1,
 int main(int argc, char** argv) {
   const char *in1 = nullptr, *in2 = nullptr;
   std::string out = "clustering_result.txt", mode, out1, out2;
-  int iters = 100, verbose = 0, only = 0, device = 0, kmer_k = 23, size_thresh = 500000;
+  int iters = 100, verbose = 0, only = 0, device = 0, kmer_k = 23, size_thresh = 500000,
+      count_min = 2;
   float min_sim = 0.80f, pval = 0.01f, vote = 0.5f;
   uint32_t seed = 12345u;
   static struct option lo[] = {{"verbose", no_argument, 0, 1},
@@ -323,6 +350,7 @@ int main(int argc, char** argv) {
       case 'o': out1 = optarg; break;
       case 'p': out2 = optarg; break;
       case 'K': kmer_k = atoi(optarg); break;
+      case 'C': count_min = atoi(optarg); break;
       case 'S': size_thresh = atoi(optarg); break;
       case 'P': pval = (float)atof(optarg); break;
       case 'V': vote = (float)atof(optarg); break;
@@ -337,18 +365,19 @@ int main(int argc, char** argv) {
   }
   if (argc < 2 || !in1 || !in2) {
     fprintf(stderr, "usage: kmerLSH -a A.txt -b B.txt [-o A -p B] [-I iters] [-N min_sim] [-K k] "
-                    "[-S size] [-P pval] [-V vote] [-F out] [-M C|E] [--only]\n");
+                    "[-C count_min] [-S size] [-P pval] [-V vote] [-F out] [-M K|B|C|E] [--only]\n");
     return 1;
   }
-  if (mode != "B" && mode != "C" && mode != "E") {
-    fprintf(stderr, "kmerLSH (gfx950): modes B (k-mer table from KMC databases), C (clustering) and "
-                    "E (extraction) are implemented; K (running the KMC counter) is not: count "
-                    "with KMC, then pass -M B\n");
+  if (!mode.empty() && mode != "K" && mode != "B" && mode != "C" && mode != "E") {
+    fprintf(stderr, "kmerLSH (gfx950): -M takes K (k-mer table from FASTQ files), B (k-mer table "
+                    "from KMC databases), C (clustering) or E (extraction)\n");
     return 1;
   }
   // app/kmerLSH.cc:234-275: --only runs the named mode; without it the later modes follow
-  const bool building = mode == "B", clustering = mode == "C" || (mode == "B" && !only);
-  const bool extracting = mode == "E" || !only;
+  const bool counting = mode.empty() || mode == "K";
+  const bool building = mode == "B" || counting;
+  const bool clustering = mode == "C" || (building && !(only && !mode.empty()));
+  const bool extracting = mode == "E" || !only || mode.empty();  // --only without -M names no mode
   const auto t0 = std::chrono::steady_clock::now();
   const int d = count_lines(in1) + count_lines(in2);
   if (building) {
@@ -358,7 +387,8 @@ int main(int argc, char** argv) {
       fprintf(stderr, "kmerLSH: %s\n", klsh_last_error());
       return 2;
     }
-    const int rc = run_build(ctx, in1, in2, kmer_k, verbose);
+    const int rc = counting ? run_count(ctx, in1, in2, kmer_k, count_min, verbose)
+                            : run_build(ctx, in1, in2, kmer_k, verbose);
     klsh_destroy(ctx);
     if (rc || (!clustering && !extracting)) return rc;
   }

@@ -215,6 +215,8 @@ struct klsh_ctx {
   uint64_t last_hash_close = 0;
   // klsh_build_khtable's test hooks and reach counters (klsh_kmc.cpp)
   klsh::KmcHooks kmc;
+  // klsh_count_khtable's (klsh_kcount.cpp)
+  klsh::KcountHooks kcount;
 
   ~klsh_ctx() { release(); }
 
@@ -766,6 +768,7 @@ namespace klsh {
 int ctx_device(const klsh_ctx* ctx) { return ctx->device; }
 hipStream_t ctx_stream(const klsh_ctx* ctx) { return ctx->stream; }
 KmcHooks& ctx_kmc(klsh_ctx* ctx) { return ctx->kmc; }
+KcountHooks& ctx_kcount(klsh_ctx* ctx) { return ctx->kcount; }
 int set_error(int code, const char* msg) { return fail(code, msg); }
 }  // namespace klsh
 
@@ -2002,6 +2005,24 @@ int klsh_set_option(klsh_ctx* ctx, const char* name, int64_t value) {
     if (!value) std::vector<uint64_t>().swap(ctx->kmc.first);
     return flag(&ctx->kmc.keep_first);
   }
+  if (n == "kcount_batch_reads") {
+    if (value < 0) return fail(KLSH_E_ARG, "kcount_batch_reads must be >= 0");
+    ctx->kcount.batch_reads = (uint64_t)value;
+    return 0;
+  }
+  if (n == "kcount_table_slots") {
+    if (value != 0 && (value < 1024 || value > (1ll << 32) || (value & (value - 1))))
+      return fail(KLSH_E_ARG, "kcount_table_slots must be 0 or a power of two in [1024, 2^32]");
+    ctx->kcount.table_slots = (uint64_t)value;
+    return 0;
+  }
+  if (n == "kcount_keep_listing") {
+    if (!value) {
+      std::vector<std::vector<uint64_t>>().swap(ctx->kcount.values);
+      std::vector<std::vector<uint32_t>>().swap(ctx->kcount.counts);
+    }
+    return flag(&ctx->kcount.keep_listing);
+  }
   if (n == "h16_grid") return grid(&ctx->pw.h16_grid);
   if (n == "h16_segcap") return grid(&ctx->pw.segcap);
   if (n == "wide_grid") return grid(&ctx->pw.wide_grid);
@@ -2063,6 +2084,13 @@ int klsh_get_option(klsh_ctx* ctx, const char* name, int64_t* value) {
   else if (n == "kmc_keep_first") *value = ctx->kmc.keep_first;
   else if (n == "kmc_decode_launches") *value = (int64_t)ctx->kmc.decode_launches;
   else if (n == "kmc_high_sort") *value = ctx->kmc.high_sort;
+  else if (n == "kcount_batch_reads") *value = (int64_t)ctx->kcount.batch_reads;
+  else if (n == "kcount_table_slots") *value = (int64_t)ctx->kcount.table_slots;
+  else if (n == "kcount_keep_listing") *value = ctx->kcount.keep_listing;
+  else if (n == "kcount_batches") *value = (int64_t)ctx->kcount.batches;
+  else if (n == "kcount_rehashes") *value = (int64_t)ctx->kcount.rehashes;
+  else if (n == "kcount_peak_slots") *value = (int64_t)ctx->kcount.peak_slots;
+  else if (n == "kcount_window") *value = (int64_t)klsh::kKcountWindow;
   else if (n == "h16_grid") *value = ctx->pw.h16_grid;
   else if (n == "h16_segcap") *value = ctx->pw.segcap;
   else if (n == "wide_grid") *value = ctx->pw.wide_grid;

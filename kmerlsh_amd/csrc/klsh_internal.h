@@ -478,10 +478,70 @@ struct KmcHooks {
   std::vector<uint64_t> first;   // distinct canonical k-mers by first ordinal
 };
 
-// The engine's context, for the other host translation units (klsh_extract.cpp, klsh_kmc.cpp).
+// The records of a set of samples as the table build streams them, twice: pass 0 (the union, in
+// first-appearance order) and pass 1 (the counts).  klsh_build_khtable decodes KMC databases
+// (klsh_kmc.cpp), klsh_count_khtable hands over the listings it counted (klsh_kcount.cpp).
+// Per pass and sample: begin, then feed for r0 = 0, chunk, 2 chunk, ... below total, then end.
+class KhSource {
+ public:
+  virtual ~KhSource() {}
+  virtual uint64_t total(int j) const = 0;  // records of sample j (its ordinals: base .. + total)
+  virtual uint64_t chunk(int j) const = 0;  // records per feed, at most
+  virtual int begin(int j, int pass, hipStream_t s) = 0;
+  // records [r0, r0 + n) of the sample on the device: *rep their canonical images (all ones = not
+  // listed), *cnt their counters; queued on s, valid until the next feed
+  virtual int feed(int j, int pass, uint64_t r0, uint64_t n, const uint64_t** rep,
+                   const uint32_t** cnt, hipStream_t s) = 0;
+  // host work on the chunk just fed, while the device runs it (the stream is synchronized after)
+  virtual void fed(int j, int pass, uint64_t n) {}
+  // pass 0: *listed = records listed; pass 1: *coverage = float running sum of log(count) in
+  // listing order (kmer/kmc_reader.cc:143)
+  virtual int end(int j, int pass, uint64_t* listed, float* coverage, hipStream_t s) = 0;
+};
+// The table of those records (buildKHtable, io/ioHT.cc:83-199): union in first-appearance order,
+// the reference's libcuckoo row order, kmer_set.hex / kmer_count.bin / kmer_count.log in out_dir.
+// Fills st's kmap_size, records, records_listed, order_ms.
+int khtable_run(klsh_ctx* ctx, KhSource& src, int n_samples, int k, const char* out_dir,
+                klsh_khtable_stats* st);
+
+// ---- mode K (klsh_kcount.hip): counting a sample's canonical k-mers -------------------------
+constexpr uint32_t kKcountWindow = 2048;  // k-mer positions per LDS window (per wave)
+// reads seq[off[r] .. off[r+1]) counted into the table (keys: mask + 1 slots, all ones = empty;
+// cnt: their occurrence counts); ctr[0] += slots claimed, ctr[1] += valid k-mer windows
+void launch_kcount_reads(const uint8_t* seq, const uint64_t* off, uint64_t n, int k, uint64_t* keys,
+                         uint32_t* cnt, uint64_t mask, uint64_t* ctr, hipStream_t s);
+// every entry of the old table into the (empty) new one
+void launch_kcount_rehash(const uint64_t* okeys, const uint32_t* ocnt, uint64_t ocap, uint64_t* keys,
+                          uint32_t* cnt, uint64_t mask, hipStream_t s);
+// slots with count >= count_min -> (low word of their KMC value, slot), *n_out of them
+void launch_kcount_collect(const uint64_t* keys, const uint32_t* cnt, uint64_t cap,
+                           uint32_t count_min, uint32_t* lo, uint32_t* slot, uint32_t* n_out,
+                           hipStream_t s);
+void launch_kcount_hi(const uint64_t* keys, const uint32_t* slots, uint64_t n, uint32_t* hi,
+                      hipStream_t s);
+// the listing in `order`: KMC value, canonical Kmer image, min(count, 65535)
+void launch_kcount_emit(const uint64_t* keys, const uint32_t* cnt, const uint32_t* order, uint64_t n,
+                        int k, uint64_t* val, uint64_t* rep, uint32_t* out_cnt, hipStream_t s);
+
+// klsh_count_khtable's test hooks and what its last call on the context reached (options
+// "kcount_batch_reads", "kcount_table_slots", "kcount_keep_listing"; read-only "kcount_batches",
+// "kcount_rehashes", "kcount_peak_slots", "kcount_window"; klsh_kcount_listing).
+struct KcountHooks {
+  uint64_t batch_reads = 0;   // reads per batch (0 = 2^18)
+  uint64_t table_slots = 0;   // a sample's initial table (0 = 2^22 slots)
+  bool keep_listing = false;  // keep the per-sample listings of the next calls
+  uint64_t batches = 0, rehashes = 0;
+  uint64_t peak_slots = 0;    // the largest sample table of the last call
+  std::vector<std::vector<uint64_t>> values;  // per sample: the listed KMC values, ascending
+  std::vector<std::vector<uint32_t>> counts;
+};
+
+// The engine's context, for the other host translation units (klsh_extract.cpp, klsh_kmc.cpp,
+// klsh_kcount.cpp).
 int ctx_device(const klsh_ctx* ctx);
 hipStream_t ctx_stream(const klsh_ctx* ctx);
 KmcHooks& ctx_kmc(klsh_ctx* ctx);
+KcountHooks& ctx_kcount(klsh_ctx* ctx);
 int set_error(int code, const char* msg);  // sets klsh_last_error(), returns code
 
 }  // namespace klsh

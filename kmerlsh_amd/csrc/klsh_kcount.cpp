@@ -1,0 +1,396 @@
+// Mode K behind the C ABI (include/klsh.h): kmer_set.hex / kmer_count.bin / kmer_count.log from
+// the samples' FASTQ files, with no external k-mer counter (reference buildKHtable with
+// kmc = true, io/ioHT.cc:83-199, which runs `kmc -k<K> -r -cs65535 -ci<C>` per sample and then
+// reads the databases back).
+//
+// Per sample: the host parses a batch of reads (klsh_fastq_next) while the GPU counts the
+// previous one into the sample's hash table (klsh_kcount.hip), which doubles between batches
+// when the next batch could load it past one half.  After the last batch the entries with
+// count >= count_min are sorted by their KMC value (two stable radix passes, low word then high
+// word): the listing of a KMC1-layout database, the convention of DESIGN.md §8.  The listings
+// stay on the device until every sample is counted; the table build of mode B (klsh::khtable_run,
+// klsh_kmc.cpp) then streams them as it streams decoded database records.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <chrono>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "klsh.h"
+#include "klsh_internal.h"
+
+namespace {
+
+using klsh::set_error;
+
+double now_ms() {
+  return std::chrono::duration<double, std::milli>(
+             std::chrono::steady_clock::now().time_since_epoch())
+      .count();
+}
+
+#define KLSH_CRET(call)                                                                   \
+  do {                                                                                    \
+    hipError_t e_ = (call);                                                               \
+    if (e_ != hipSuccess)                                                                 \
+      return set_error(KLSH_E_HIP, (std::string(#call) + " -> " + hipGetErrorString(e_)).c_str()); \
+  } while (0)
+
+constexpr uint64_t kBatchReads = 1ull << 18, kTableSlots = 1ull << 22;
+
+// One sample's listing on the device, and its coverage (the float running sum of
+// log((double)count) in listing order, kmer/kmc_reader.cc:143).
+struct Listing {
+  uint64_t n = 0;
+  uint64_t* rep = nullptr;
+  uint32_t* cnt = nullptr;
+  float coverage = 0.0f;
+};
+
+class ListingSource : public klsh::KhSource {
+ public:
+  std::vector<Listing> ls;
+  ~ListingSource() override {
+    for (auto& l : ls) {
+      if (l.rep) (void)hipFree(l.rep);
+      if (l.cnt) (void)hipFree(l.cnt);
+    }
+  }
+  uint64_t total(int j) const override { return ls[j].n; }
+  uint64_t chunk(int j) const override { return ls[j].n ? ls[j].n : 1; }
+  int begin(int, int, hipStream_t) override { return KLSH_OK; }
+  int feed(int j, int, uint64_t r0, uint64_t, const uint64_t** rep, const uint32_t** cnt,
+           hipStream_t) override {
+    *rep = ls[j].rep + r0;
+    *cnt = ls[j].cnt + r0;
+    return KLSH_OK;
+  }
+  int end(int j, int pass, uint64_t* listed, float* coverage, hipStream_t) override {
+    if (pass == 0) *listed = ls[j].n;
+    else *coverage = ls[j].coverage;
+    return KLSH_OK;
+  }
+};
+
+// The counting of one call: the sample table, the two batch slots, the sort buffers.
+class Counter {
+ public:
+  Counter(klsh_ctx* ctx, int k, uint32_t count_min, klsh_kcount_stats& st)
+      : hooks_(klsh::ctx_kcount(ctx)), s_(klsh::ctx_stream(ctx)), k_(k), count_min_(count_min),
+        st_(st) {}
+  ~Counter() {
+    for (auto& sl : slot_) {
+      if (sl.dseq) (void)hipFree(sl.dseq);
+      if (sl.doff) (void)hipFree(sl.doff);
+      if (sl.e0) (void)hipEventDestroy(sl.e0);
+      if (sl.e1) (void)hipEventDestroy(sl.e1);
+    }
+    for (void* p : {(void*)keys_, (void*)cnt_, (void*)ctr_, (void*)lo_, (void*)lo2_, (void*)sl_,
+                    (void*)sl2_, (void*)ws_, (void*)val_})
+      if (p) (void)hipFree(p);
+    if (hctr_) (void)hipHostFree(hctr_);
+  }
+
+  int init() {
+    cap_ = hooks_.table_slots ? hooks_.table_slots : kTableSlots;
+    hooks_.peak_slots = cap_;
+    KLSH_CRET(hipMalloc((void**)&keys_, cap_ * 8));
+    KLSH_CRET(hipMalloc((void**)&cnt_, cap_ * 4));
+    KLSH_CRET(hipMalloc((void**)&ctr_, 64));
+    KLSH_CRET(hipHostMalloc((void**)&hctr_, 64, hipHostMallocDefault));
+    for (auto& sl : slot_) {
+      KLSH_CRET(hipEventCreate(&sl.e0));
+      KLSH_CRET(hipEventCreate(&sl.e1));
+    }
+    return KLSH_OK;
+  }
+
+  // path's reads counted, the listing left in *out
+  int sample(const char* path, Listing* out, std::vector<uint64_t>* keep_val,
+             std::vector<uint32_t>* keep_cnt) {
+    int err = KLSH_OK;
+    klsh_fastq* f = klsh_fastq_open(path, &err);
+    if (!f) return err;
+    const int rc = count(f);
+    klsh_fastq_close(f);
+    if (rc) return rc;
+    return list(out, keep_val, keep_cnt);
+  }
+
+ private:
+  struct Slot {
+    std::vector<char> seq;
+    std::vector<uint64_t> off;
+    uint8_t* dseq = nullptr;
+    uint64_t* doff = nullptr;
+    uint64_t cap_b = 0, cap_r = 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+  } slot_[2];
+  klsh::KcountHooks& hooks_;
+  hipStream_t s_;
+  int k_;
+  uint32_t count_min_;
+  klsh_kcount_stats& st_;
+  uint64_t cap_ = 0, occ_ = 0, pos_ = 0;
+  uint64_t *keys_ = nullptr, *ctr_ = nullptr, *hctr_ = nullptr, *val_ = nullptr;
+  uint32_t *cnt_ = nullptr, *lo_ = nullptr, *lo2_ = nullptr, *sl_ = nullptr, *sl2_ = nullptr,
+           *ws_ = nullptr;
+  uint64_t sort_cap_ = 0;
+
+  // the table doubled until `more` further k-mers keep it at most half full
+  int grow(uint64_t more) {
+    while (occ_ + more > cap_ / 2) {
+      const uint64_t ncap = cap_ * 2;
+      if (ncap > (1ull << 32)) return set_error(KLSH_E_RANGE, "more than 2^31 distinct k-mers in a sample");
+      uint64_t* nkeys = nullptr;
+      uint32_t* ncnt = nullptr;
+      if (hipMalloc((void**)&nkeys, ncap * 8) != hipSuccess ||
+          hipMalloc((void**)&ncnt, ncap * 4) != hipSuccess) {
+        if (nkeys) (void)hipFree(nkeys);
+        return set_error(KLSH_E_NOMEM, "count_khtable: the grown k-mer table");
+      }
+      hipError_t e = hipMemsetAsync(nkeys, 0xFF, ncap * 8, s_);
+      if (e == hipSuccess) e = hipMemsetAsync(ncnt, 0, ncap * 4, s_);
+      if (e == hipSuccess) {
+        klsh::launch_kcount_rehash(keys_, cnt_, cap_, nkeys, ncnt, ncap - 1, s_);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = hipStreamSynchronize(s_);
+      if (e != hipSuccess) {
+        (void)hipFree(nkeys);
+        (void)hipFree(ncnt);
+        return set_error(KLSH_E_HIP, (std::string("count_khtable: rehash -> ") + hipGetErrorString(e)).c_str());
+      }
+      (void)hipFree(keys_);
+      (void)hipFree(cnt_);
+      keys_ = nkeys;
+      cnt_ = ncnt;
+      cap_ = ncap;
+      hooks_.peak_slots = cap_;
+      hooks_.rehashes += 1;
+      st_.rehashes += 1;
+    }
+    return KLSH_OK;
+  }
+
+  int launch(Slot& sl) {
+    const uint64_t n = sl.off.size() - 1, nb = sl.seq.size();
+    if (nb + 64 > sl.cap_b) {
+      if (sl.dseq) (void)hipFree(sl.dseq);
+      sl.dseq = nullptr;
+      sl.cap_b = 0;
+      KLSH_CRET(hipMalloc((void**)&sl.dseq, nb + nb / 4 + 64));
+      sl.cap_b = nb + nb / 4 + 64;
+    }
+    if (n + 1 > sl.cap_r) {
+      if (sl.doff) (void)hipFree(sl.doff);
+      sl.doff = nullptr;
+      sl.cap_r = 0;
+      KLSH_CRET(hipMalloc((void**)&sl.doff, (n + 1) * 8));
+      sl.cap_r = n + 1;
+    }
+    if (nb) KLSH_CRET(hipMemcpyAsync(sl.dseq, sl.seq.data(), nb, hipMemcpyHostToDevice, s_));
+    KLSH_CRET(hipMemcpyAsync(sl.doff, sl.off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s_));
+    KLSH_CRET(hipEventRecord(sl.e0, s_));
+    klsh::launch_kcount_reads(sl.dseq, sl.doff, n, k_, keys_, cnt_, cap_ - 1, ctr_, s_);
+    KLSH_CRET(hipGetLastError());
+    KLSH_CRET(hipEventRecord(sl.e1, s_));
+    KLSH_CRET(hipMemcpyAsync(hctr_, ctr_, 16, hipMemcpyDeviceToHost, s_));
+    return KLSH_OK;
+  }
+
+  // the batch in flight finished: its kernel time, the table's load and the windows so far
+  int finish(Slot& sl) {
+    KLSH_CRET(hipStreamSynchronize(s_));
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, sl.e0, sl.e1);
+    st_.kernel_ms += ms;
+    occ_ = hctr_[0];
+    pos_ = hctr_[1];
+    return KLSH_OK;
+  }
+
+  int count(klsh_fastq* f) {
+    occ_ = pos_ = 0;
+    KLSH_CRET(hipMemsetAsync(keys_, 0xFF, cap_ * 8, s_));
+    KLSH_CRET(hipMemsetAsync(cnt_, 0, cap_ * 4, s_));
+    KLSH_CRET(hipMemsetAsync(ctr_, 0, 64, s_));
+    const uint64_t per = hooks_.batch_reads ? hooks_.batch_reads : kBatchReads;
+    int cur = 0, rc = KLSH_OK;
+    bool pending = false;
+    while (true) {
+      // the host parses this batch while the GPU counts the previous one
+      const double tp = now_ms();
+      const char* seq = nullptr;
+      const uint64_t* off = nullptr;
+      const int64_t n = klsh_fastq_next(f, per, &seq, &off, nullptr, nullptr, nullptr, nullptr);
+      if (n < 0) {
+        rc = (int)n;
+        break;
+      }
+      Slot& sl = slot_[cur];
+      uint64_t windows = 0;  // an upper bound of the batch's new k-mers
+      if (n > 0) {
+        sl.seq.assign(seq + off[0], seq + off[n]);
+        sl.off.resize((size_t)n + 1);
+        for (int64_t i = 0; i <= n; ++i) sl.off[i] = off[i] - off[0];
+        for (int64_t i = 0; i < n; ++i) {
+          const uint64_t len = sl.off[i + 1] - sl.off[i];
+          if (len >= (uint64_t)k_) windows += len - (uint64_t)k_ + 1;
+        }
+        st_.reads += (uint64_t)n;
+        st_.bases += sl.seq.size();
+      }
+      st_.parse_ms += now_ms() - tp;
+      if (pending && (rc = finish(slot_[cur ^ 1]))) break;
+      pending = false;
+      if (n == 0) break;
+      if ((rc = grow(windows))) break;
+      if ((rc = launch(sl))) break;
+      pending = true;
+      hooks_.batches += 1;
+      st_.batches += 1;
+      cur ^= 1;
+    }
+    if (rc) (void)hipStreamSynchronize(s_);  // nothing of this sample stays queued
+    return rc;
+  }
+
+  int list(Listing* out, std::vector<uint64_t>* keep_val, std::vector<uint32_t>* keep_cnt) {
+    st_.positions += pos_;
+    st_.distinct += occ_;
+    if (occ_ + 64 > sort_cap_) {
+      for (void* p : {(void*)lo_, (void*)lo2_, (void*)sl_, (void*)sl2_, (void*)ws_, (void*)val_})
+        if (p) (void)hipFree(p);
+      lo_ = lo2_ = sl_ = sl2_ = ws_ = nullptr;
+      val_ = nullptr;
+      sort_cap_ = 0;
+      const uint64_t c = occ_ + occ_ / 4 + 64;
+      KLSH_CRET(hipMalloc((void**)&lo_, c * 4));
+      KLSH_CRET(hipMalloc((void**)&lo2_, c * 4));
+      KLSH_CRET(hipMalloc((void**)&sl_, c * 4));
+      KLSH_CRET(hipMalloc((void**)&sl2_, c * 4));
+      KLSH_CRET(hipMalloc((void**)&ws_, klsh::sort_ws_words(c) * 4));
+      KLSH_CRET(hipMalloc((void**)&val_, c * 8));
+      sort_cap_ = c;
+    }
+    uint32_t* nout = reinterpret_cast<uint32_t*>(ctr_ + 4);
+    uint32_t n = 0;
+    KLSH_CRET(hipMemsetAsync(nout, 0, 4, s_));
+    klsh::launch_kcount_collect(keys_, cnt_, cap_, count_min_, lo_, sl_, nout, s_);
+    KLSH_CRET(hipGetLastError());
+    KLSH_CRET(hipMemcpyAsync(&n, nout, 4, hipMemcpyDeviceToHost, s_));
+    KLSH_CRET(hipStreamSynchronize(s_));
+    // ascending KMC value: two stable 32-bit radix sorts, low word then high word
+    uint32_t *ok = lo_, *ov = sl_;
+    if (n) klsh::radix_sort(lo_, sl_, lo2_, sl2_, n, k_ < 16 ? 2 * k_ : 32, ws_, &ok, &ov, s_);
+    if (n && k_ > 16) {
+      uint32_t* hk = ok == lo_ ? lo2_ : lo_;  // the free key buffer
+      uint32_t* hv = ov == sl_ ? sl2_ : sl_;
+      klsh::launch_kcount_hi(keys_, ov, n, hk, s_);
+      uint32_t *ok2 = nullptr, *ov2 = nullptr;
+      klsh::radix_sort(hk, ov, ok, hv, n, 2 * k_ - 32, ws_, &ok2, &ov2, s_);
+      ov = ov2;
+    }
+    KLSH_CRET(hipGetLastError());
+    out->n = n;
+    KLSH_CRET(hipMalloc((void**)&out->rep, (uint64_t)(n ? n : 1) * 8));
+    KLSH_CRET(hipMalloc((void**)&out->cnt, (uint64_t)(n ? n : 1) * 4));
+    klsh::launch_kcount_emit(keys_, cnt_, ov, n, k_, val_, out->rep, out->cnt, s_);
+    KLSH_CRET(hipGetLastError());
+    std::vector<uint32_t> hcnt(n);
+    if (n) KLSH_CRET(hipMemcpyAsync(hcnt.data(), out->cnt, n * 4ull, hipMemcpyDeviceToHost, s_));
+    if (keep_val) {
+      keep_val->resize(n);
+      if (n) KLSH_CRET(hipMemcpyAsync(keep_val->data(), val_, n * 8ull, hipMemcpyDeviceToHost, s_));
+    }
+    KLSH_CRET(hipStreamSynchronize(s_));
+    float cov = 0.0f;
+    for (uint32_t i = 0; i < n; ++i) cov += log((double)hcnt[i]);
+    out->coverage = cov;
+    st_.listed += n;
+    if (keep_cnt) keep_cnt->swap(hcnt);
+    return KLSH_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" int klsh_kcount_listing(klsh_ctx* ctx, int sample, uint64_t* kmc_values,
+                                   uint32_t* counts, uint64_t* n) {
+  if (!ctx || !n) return set_error(KLSH_E_ARG, "null argument");
+  const klsh::KcountHooks& h = klsh::ctx_kcount(ctx);
+  if (sample < 0 || (size_t)sample >= h.values.size())
+    return set_error(KLSH_E_ARG, "klsh_kcount_listing: no kept listing of that sample");
+  const std::vector<uint64_t>& v = h.values[sample];
+  const uint64_t room = *n;
+  *n = v.size();
+  if (!kmc_values && !counts) return KLSH_OK;
+  if (room < v.size()) return set_error(KLSH_E_RANGE, "klsh_kcount_listing: output too small");
+  if (kmc_values && !v.empty()) memcpy(kmc_values, v.data(), v.size() * 8);
+  if (counts && !v.empty()) memcpy(counts, h.counts[sample].data(), v.size() * 4);
+  return KLSH_OK;
+}
+
+extern "C" int klsh_count_khtable(klsh_ctx* ctx, const char* const* fastq_paths, int n_samples,
+                                  int k, int count_min, const char* out_dir,
+                                  klsh_kcount_stats* st) {
+  if (!ctx || !fastq_paths || n_samples <= 0) return set_error(KLSH_E_ARG, "bad argument");
+  if (k < 1 || k > 32) return set_error(KLSH_E_RANGE, "k must be in [1, 32] (Kmer::MAX_K)");
+  const double t_start = now_ms();
+  if (st && st->struct_size != sizeof(klsh_kcount_stats))
+    return set_error(KLSH_E_ARG, "klsh_kcount_stats.struct_size != sizeof: built against another klsh.h");
+  klsh_kcount_stats local{};
+  local.struct_size = sizeof(local);
+  klsh::KcountHooks& hooks = klsh::ctx_kcount(ctx);  // test hooks; what this call reaches
+  klsh::KmcHooks& bhooks = klsh::ctx_kmc(ctx);
+  hooks.batches = hooks.rehashes = hooks.peak_slots = 0;
+  hooks.values.clear();
+  hooks.counts.clear();
+  bhooks.decode_launches = 0;
+  bhooks.high_sort = 0;
+  bhooks.first.clear();
+  for (int j = 0; j < n_samples; ++j) {  // a missing file fails before any device work
+    FILE* f = fastq_paths[j] ? fopen(fastq_paths[j], "rb") : nullptr;
+    if (!f)
+      return set_error(KLSH_E_ARG, fastq_paths[j] ? (std::string("cannot open ") + fastq_paths[j]).c_str()
+                                                  : "null FASTQ path");
+    fclose(f);
+  }
+  if (hipSetDevice(klsh::ctx_device(ctx)) != hipSuccess) return set_error(KLSH_E_HIP, "hipSetDevice");
+  int rc;
+  {
+    ListingSource src;
+    src.ls.resize(n_samples);
+    if (hooks.keep_listing) {
+      hooks.values.resize(n_samples);
+      hooks.counts.resize(n_samples);
+    }
+    {
+      Counter counter(ctx, k, (uint32_t)(count_min < 1 ? 1 : count_min), local);
+      rc = counter.init();
+      for (int j = 0; j < n_samples && rc == KLSH_OK; ++j)
+        rc = counter.sample(fastq_paths[j], &src.ls[j],
+                            hooks.keep_listing ? &hooks.values[j] : nullptr,
+                            hooks.keep_listing ? &hooks.counts[j] : nullptr);
+    }  // the sample table is freed before the union's
+    if (rc == KLSH_OK) {
+      klsh_khtable_stats bst{};
+      bst.struct_size = sizeof(bst);
+      rc = klsh::khtable_run(ctx, src, n_samples, k, out_dir, &bst);
+      local.kmap_size = bst.kmap_size;
+      local.order_ms = bst.order_ms;
+    }
+    if (rc != KLSH_OK) {
+      hooks.values.clear();
+      hooks.counts.clear();
+    }
+  }
+  local.total_ms = now_ms() - t_start;
+  if (st) *st = local;
+  return rc;
+}

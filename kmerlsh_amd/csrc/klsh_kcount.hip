@@ -1,0 +1,228 @@
+// Mode K on gfx950: counting the canonical k-mers of a sample's reads, what the reference leaves to
+// the external `kmc -k<K> -r -cs65535 -ci<C>` (io/ioHT.cc:100-103).
+//
+// A k-mer is its KMC value (base 0 most significant, A < C < G < T); the canonical one is the
+// smaller of the window and its reverse complement.  A character that is not one of ACGTacgt breaks
+// the read: no window spans it (KMC's rule; k_check_reads' "anything else is A" is another rule).
+//
+//   k_kcount_reads    one wave per read: the read's base codes staged in LDS in windows (one byte
+//                     each, 4 = break), one lane per k-mer position building its value from LDS;
+//                     equal keys of neighbouring lanes (a homopolymer or short-period run) are
+//                     combined, and the first lane of a run probes the table (open addressing,
+//                     64-bit CAS on the key; all ones = empty, never canonical: the all-T k-mer's
+//                     reverse complement is 0) and adds the run's length to the slot's 32-bit count
+//   k_kcount_rehash   keys and counts into a table of twice the slots (between batches)
+//   k_kcount_collect  slots with count >= count_min -> (low word of the value, slot)
+//   k_kcount_hi       the values' high words, for the second sort pass (k > 16)
+//   k_kcount_emit     the listing in sorted order: value, rep image, min(count, 65535)
+//
+// The count word never wraps: a lane adds only while the count it sees is below 65535, so a slot
+// ends at most one in-flight add per wave above that (each at most 64), and every slot below
+// 65535 is exact.  The same test bounds the same-address adds of a poly-A read: after 65535 its
+// lanes only read.
+//
+// Bound: the probes, as in mode E — one random 8-B key access (and one 4-B count add) per run of
+// equal k-mers; the sequence is read once.  A sample's table is far larger than mode E's set, so
+// the accesses go to HBM, not L2.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "klsh_internal.h"
+#include "klsh_kmer.h"
+
+namespace klsh {
+
+constexpr uint64_t kKcEmpty = ~0ull;
+constexpr int kKcWaves = 4;  // waves per workgroup, each on its own reads
+
+__device__ __forceinline__ uint64_t kc_hash(uint64_t k) {  // murmur3 finalizer
+  k ^= k >> 33;
+  k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33;
+  k *= 0xc4ceb9fe1a85ec53ull;
+  k ^= k >> 33;
+  return k;
+}
+
+__device__ __forceinline__ uint32_t kc_code(uint32_t c) {
+  c |= 0x20u;  // the lower-case letter; no other character maps onto a, c, g, t
+  return c == 'a' ? 0u : c == 'c' ? 1u : c == 'g' ? 2u : c == 't' ? 3u : 4u;
+}
+
+// the slot of `key`, claimed if absent (*fresh = 1 then)
+__device__ __forceinline__ uint64_t kc_slot(unsigned long long* keys, uint64_t mask, uint64_t key,
+                                            uint32_t* fresh) {
+  uint64_t h = kc_hash(key) & mask;
+  while (true) {
+    // a key never changes once set: a read of it settles the probe without an atomic
+    unsigned long long t = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == kKcEmpty) {
+      t = atomicCAS(&keys[h], (unsigned long long)kKcEmpty, (unsigned long long)key);
+      if (t == kKcEmpty) {
+        *fresh = 1u;
+        return h;
+      }
+    }
+    if (t == key) return h;
+    h = (h + 1) & mask;
+  }
+}
+
+// ctr[0] += slots claimed, ctr[1] += valid k-mer windows (one add per wave and counter)
+__global__ __launch_bounds__(256) void k_kcount_reads(const uint8_t* __restrict__ seq,
+                                                      const uint64_t* __restrict__ off, uint64_t n,
+                                                      int k, unsigned long long* keys,
+                                                      uint32_t* cnt, uint64_t mask,
+                                                      unsigned long long* ctr) {
+  __shared__ uint8_t codes[kKcWaves][kKcountWindow + 64];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint8_t* cw = codes[wv];
+  const uint64_t waves = (uint64_t)gridDim.x * kKcWaves;
+  uint32_t n_new = 0, n_pos = 0;
+  for (uint64_t r = (uint64_t)blockIdx.x * kKcWaves + wv; r < n; r += waves) {  // wave-uniform
+    const uint64_t a = off[r];
+    const uint64_t len = off[r + 1] - a;
+    if (len < (uint64_t)k) continue;
+    const uint64_t npos = len - (uint64_t)k + 1u;
+    for (uint64_t w0 = 0; w0 < npos; w0 += kKcountWindow) {
+      const uint32_t np = (uint32_t)(npos - w0 < kKcountWindow ? npos - w0 : kKcountWindow);
+      const uint32_t nb = np + (uint32_t)k - 1u;  // bases of the window (<= kKcountWindow + 31)
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      for (uint32_t q = lane; q < nb; q += 64u) cw[q] = (uint8_t)kc_code(seq[a + w0 + q]);
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      for (uint32_t p0 = 0; p0 < np; p0 += 64u) {  // wave-uniform: the lanes stay together
+        const uint32_t p = p0 + lane;
+        uint64_t v = 0;
+        uint32_t brk = p < np ? 0u : 4u;
+        if (p < np)
+          for (int i = 0; i < k; ++i) {
+            const uint32_t c = cw[p + (uint32_t)i];
+            brk |= c;
+            v = (v << 2) | (uint64_t)(c & 3u);
+          }
+        const bool valid = brk < 4u;
+        const uint64_t key = valid ? kmc_canonical(v, k) : kKcEmpty;
+        // runs of equal keys in neighbouring lanes: the first lane adds the run's length
+        const uint64_t prev = __shfl_up((unsigned long long)key, 1, 64);
+        const bool head = valid && (lane == 0u || key != prev);
+        const uint64_t hm = __ballot(head), vm = __ballot(valid);
+        n_pos += valid ? 1u : 0u;
+        if (head) {
+          const uint64_t stop = (hm | ~vm) & ~((2ull << lane) - 1ull);  // next head or break above
+          const uint32_t run = (stop ? (uint32_t)__builtin_ctzll(stop) : 64u) - lane;
+          uint32_t fresh = 0;
+          const uint64_t h = kc_slot(keys, mask, key, &fresh);
+          n_new += fresh;
+          if (__hip_atomic_load(&cnt[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 65535u)
+            atomicAdd(&cnt[h], run);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    n_new += __shfl_xor(n_new, o, 64);
+    n_pos += __shfl_xor(n_pos, o, 64);
+  }
+  if (lane == 0) {
+    if (n_new) atomicAdd(&ctr[0], (unsigned long long)n_new);
+    if (n_pos) atomicAdd(&ctr[1], (unsigned long long)n_pos);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_kcount_rehash(const uint64_t* __restrict__ okeys,
+                                                       const uint32_t* __restrict__ ocnt,
+                                                       uint64_t ocap, unsigned long long* keys,
+                                                       uint32_t* __restrict__ cnt, uint64_t mask) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < ocap; i += (uint64_t)gridDim.x * 256ull) {
+    const uint64_t key = okeys[i];
+    if (key == kKcEmpty) continue;
+    uint32_t fresh = 0;
+    const uint64_t h = kc_slot(keys, mask, key, &fresh);
+    cnt[h] = ocnt[i];  // the old table holds a key once
+  }
+}
+
+__global__ __launch_bounds__(256) void k_kcount_collect(const uint64_t* __restrict__ keys,
+                                                        const uint32_t* __restrict__ cnt,
+                                                        uint64_t cap, uint32_t count_min,
+                                                        uint32_t* __restrict__ lo,
+                                                        uint32_t* __restrict__ slot,
+                                                        uint32_t* __restrict__ n_out) {
+  // cap is a power of two >= 1024: every wave's 64 lanes are in or out of range together
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull;
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * 256ull) {
+    const uint64_t key = keys[i];
+    const bool take = key != kKcEmpty && cnt[i] >= count_min;
+    const uint64_t m = __ballot(take);
+    if (!m) continue;
+    uint32_t base = 0;  // one add per wave, not per entry (a single counter)
+    if (lane == (uint32_t)__builtin_ctzll(m)) base = atomicAdd(n_out, (uint32_t)__popcll(m));
+    base = __shfl(base, (int)__builtin_ctzll(m), 64);
+    if (take) {
+      const uint32_t o = base + (uint32_t)__popcll(m & below);
+      lo[o] = (uint32_t)key;
+      slot[o] = (uint32_t)i;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_kcount_hi(const uint64_t* __restrict__ keys,
+                                                   const uint32_t* __restrict__ slots, uint64_t n,
+                                                   uint32_t* __restrict__ hi) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull)
+    hi[i] = (uint32_t)(keys[slots[i]] >> 32);
+}
+
+__global__ __launch_bounds__(256) void k_kcount_emit(const uint64_t* __restrict__ keys,
+                                                     const uint32_t* __restrict__ cnt,
+                                                     const uint32_t* __restrict__ order, uint64_t n,
+                                                     int k, uint64_t* __restrict__ val,
+                                                     uint64_t* __restrict__ rep,
+                                                     uint32_t* __restrict__ out_cnt) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull) {
+    const uint32_t s = order[i];
+    const uint64_t v = keys[s];
+    val[i] = v;
+    rep[i] = kmc_value_rep(v, k);  // klsh_kmer.h, shared with mode B's record decode
+    out_cnt[i] = min(cnt[s], 65535u);
+  }
+}
+
+static uint32_t kc_grid(uint64_t n) {
+  const uint64_t g = (n + 255) / 256;
+  return (uint32_t)(g < 16384 ? (g ? g : 1) : 16384);
+}
+
+void launch_kcount_reads(const uint8_t* seq, const uint64_t* off, uint64_t n, int k, uint64_t* keys,
+                         uint32_t* cnt, uint64_t mask, uint64_t* ctr, hipStream_t s) {
+  if (n == 0) return;
+  // at most 4096 workgroups: each wave ends with two adds to ctr
+  const uint64_t w = (n + kKcWaves - 1) / kKcWaves, g = w < 4096 ? w : 4096;
+  k_kcount_reads<<<(uint32_t)g, 64 * kKcWaves, 0, s>>>(
+      seq, off, n, k, reinterpret_cast<unsigned long long*>(keys), cnt, mask,
+      reinterpret_cast<unsigned long long*>(ctr));
+}
+void launch_kcount_rehash(const uint64_t* okeys, const uint32_t* ocnt, uint64_t ocap, uint64_t* keys,
+                          uint32_t* cnt, uint64_t mask, hipStream_t s) {
+  k_kcount_rehash<<<kc_grid(ocap), 256, 0, s>>>(okeys, ocnt, ocap,
+                                                reinterpret_cast<unsigned long long*>(keys), cnt,
+                                                mask);
+}
+void launch_kcount_collect(const uint64_t* keys, const uint32_t* cnt, uint64_t cap,
+                           uint32_t count_min, uint32_t* lo, uint32_t* slot, uint32_t* n_out,
+                           hipStream_t s) {
+  k_kcount_collect<<<kc_grid(cap), 256, 0, s>>>(keys, cnt, cap, count_min, lo, slot, n_out);
+}
+void launch_kcount_hi(const uint64_t* keys, const uint32_t* slots, uint64_t n, uint32_t* hi,
+                      hipStream_t s) {
+  if (n) k_kcount_hi<<<kc_grid(n), 256, 0, s>>>(keys, slots, n, hi);
+}
+void launch_kcount_emit(const uint64_t* keys, const uint32_t* cnt, const uint32_t* order, uint64_t n,
+                        int k, uint64_t* val, uint64_t* rep, uint32_t* out_cnt, hipStream_t s) {
+  if (n) k_kcount_emit<<<kc_grid(n), 256, 0, s>>>(keys, cnt, order, n, k, val, rep, out_cnt);
+}
+
+}  // namespace klsh

@@ -348,129 +348,173 @@ extern "C" int klsh_khtable_first(klsh_ctx* ctx, uint64_t* images, uint64_t* n) 
       goto done;                                                                          \
     }                                                                                     \
   } while (0)
+#define KLSH_KRET(call)                                                                   \
+  do {                                                                                    \
+    hipError_t e_ = (call);                                                               \
+    if (e_ != hipSuccess)                                                                 \
+      return set_error(KLSH_E_HIP, (std::string(#call) + " -> " + hipGetErrorString(e_)).c_str()); \
+  } while (0)
 
-extern "C" int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, int n_samples,
-                                  int k, const char* out_dir, klsh_khtable_stats* st) {
-  if (!ctx || !kmc_names || n_samples <= 0) return set_error(KLSH_E_ARG, "bad argument");
-  if (k < 1 || k > 32) return set_error(KLSH_E_RANGE, "k must be in [1, 32] (Kmer::MAX_K)");
-  const double t_start = now_ms();
-  if (st && st->struct_size != sizeof(klsh_khtable_stats))
-    return set_error(KLSH_E_ARG, "klsh_khtable_stats.struct_size != sizeof: built against another klsh.h");
-  klsh_khtable_stats local{};
-  local.struct_size = sizeof(local);
-  klsh::KmcHooks& hooks = klsh::ctx_kmc(ctx);  // test hooks; what this call reaches
-  hooks.decode_launches = 0;
-  hooks.high_sort = 0;
-  hooks.first.clear();
-  std::vector<KmcDb> dbs(n_samples);
-  uint64_t records = 0;
-  for (int j = 0; j < n_samples; ++j) {
-    if (!kmc_names[j] || !dbs[j].open(kmc_names[j]))
-      return set_error(KLSH_E_ARG, kmc_names[j] ? dbs[j].err.c_str() : "null database name");
-    if ((int)dbs[j].k != k)
-      return set_error(KLSH_E_ARG, (std::string(kmc_names[j]) + ": k-mer length differs from -K").c_str());
-    records += dbs[j].total;
+namespace {
+
+// klsh_build_khtable's records: every .kmc_suf streamed in chunks (the files are the I/O) and
+// decoded on the device (k_kmc_decode).
+class KmcFileSource : public klsh::KhSource {
+ public:
+  static constexpr uint64_t kChunkBytes = 64ull << 20;
+  KmcFileSource(const std::vector<KmcDb>& dbs, klsh::KmcHooks& hooks, klsh_khtable_stats& st)
+      : dbs_(dbs), hooks_(hooks), st_(st), hrec_(kChunkBytes) {}
+  ~KmcFileSource() override {
+    if (f_) fclose(f_);
+    for (void* ptr : {(void*)drec_, (void*)drep_, (void*)dcnt_, (void*)dlut_, (void*)nvalid_})
+      if (ptr) (void)hipFree(ptr);
   }
-  if (hipSetDevice(klsh::ctx_device(ctx)) != hipSuccess) return set_error(KLSH_E_HIP, "hipSetDevice");
+  int alloc() {
+    uint64_t max_lut = 0, max_chunk_recs = 0;
+    for (const auto& db : dbs_) {
+      max_lut = std::max<uint64_t>(max_lut, db.lut.size());
+      max_chunk_recs = std::max<uint64_t>(max_chunk_recs, kChunkBytes / db.params().rec_size + 1);
+    }
+    KLSH_KRET(hipMalloc((void**)&drec_, kChunkBytes + 64));
+    KLSH_KRET(hipMalloc((void**)&drep_, max_chunk_recs * 8));
+    KLSH_KRET(hipMalloc((void**)&dcnt_, max_chunk_recs * 4));
+    KLSH_KRET(hipMalloc((void**)&dlut_, max_lut * 8));
+    KLSH_KRET(hipMalloc((void**)&nvalid_, 64));
+    return KLSH_OK;
+  }
+  uint64_t total(int j) const override { return dbs_[j].total; }
+  uint64_t chunk(int j) const override {
+    uint64_t per_chunk = kChunkBytes / dbs_[j].params().rec_size;  // what hrec / drec / drep / dcnt hold
+    if (hooks_.chunk_records) per_chunk = std::min<uint64_t>(per_chunk, hooks_.chunk_records);
+    return per_chunk;
+  }
+  int begin(int j, int pass, hipStream_t s) override {
+    const KmcDb& db = dbs_[j];
+    kp_ = db.params();
+    cov_ = 0.0f;
+    KLSH_KRET(hipMemcpyAsync(dlut_, db.lut.data(), db.lut.size() * 8, hipMemcpyHostToDevice, s));
+    KLSH_KRET(hipMemsetAsync(nvalid_, 0, 4, s));
+    f_ = fopen(db.suf.c_str(), "rb");
+    if (!f_) return set_error(KLSH_E_ARG, ("cannot open " + db.suf).c_str());
+    char mark[4];
+    if (fread(mark, 1, 4, f_) != 4 || memcmp(mark, "KMCS", 4))
+      return set_error(KLSH_E_ARG, (db.suf + ": bad marker").c_str());
+    return KLSH_OK;
+  }
+  int feed(int j, int pass, uint64_t r0, uint64_t n, const uint64_t** rep, const uint32_t** cnt,
+           hipStream_t s) override {
+    const KmcDb& db = dbs_[j];
+    const double tio = now_ms();
+    if (fread(hrec_.data(), kp_.rec_size, n, f_) != n)
+      return set_error(KLSH_E_ARG, (db.suf + ": short file").c_str());
+    st_.io_ms += now_ms() - tio;
+    KLSH_KRET(hipMemcpyAsync(drec_, hrec_.data(), n * kp_.rec_size, hipMemcpyHostToDevice, s));
+    klsh::launch_kmc_decode(drec_, n, r0, kp_, dlut_, db.lut.size(), drep_, dcnt_, nvalid_, s);
+    if (pass == 0) ++hooks_.decode_launches;
+    *rep = drep_;
+    *cnt = dcnt_;
+    return KLSH_OK;
+  }
+  void fed(int j, int pass, uint64_t n) override {
+    if (pass != 1) return;  // tot_coverage += log(cnt), float, file order (kmc_reader.cc:143)
+    const KmcDb& db = dbs_[j];
+    for (uint64_t i = 0; i < n; ++i) {
+      const uint8_t* q = hrec_.data() + i * kp_.rec_size + kp_.sufix_size;
+      uint32_t c = 0;
+      for (uint32_t b = 0; b < kp_.counter_size; ++b) c |= (uint32_t)q[b] << (8 * b);
+      if (c >= db.min_count && (uint64_t)c <= db.max_count) cov_ += log((double)c);
+    }
+  }
+  int end(int j, int pass, uint64_t* listed, float* coverage, hipStream_t s) override {
+    fclose(f_);
+    f_ = nullptr;
+    st_.records += dbs_[j].total;
+    if (pass == 0) {
+      uint32_t nv = 0;
+      KLSH_KRET(hipMemcpy(&nv, nvalid_, 4, hipMemcpyDeviceToHost));
+      *listed = nv;
+    } else {
+      *coverage = cov_;
+    }
+    return KLSH_OK;
+  }
+
+ private:
+  const std::vector<KmcDb>& dbs_;
+  klsh::KmcHooks& hooks_;
+  klsh_khtable_stats& st_;
+  std::vector<uint8_t> hrec_;
+  klsh::KmcParams kp_{};
+  float cov_ = 0.0f;
+  FILE* f_ = nullptr;
+  uint8_t* drec_ = nullptr;
+  uint64_t *drep_ = nullptr, *dlut_ = nullptr;
+  uint32_t *dcnt_ = nullptr, *nvalid_ = nullptr;
+};
+
+}  // namespace
+
+int klsh::khtable_run(klsh_ctx* ctx, klsh::KhSource& src, int n_samples, int k, const char* out_dir,
+                      klsh_khtable_stats* st) {
+  klsh_khtable_stats& local = *st;
+  klsh::KmcHooks& hooks = klsh::ctx_kmc(ctx);
   const hipStream_t s = klsh::ctx_stream(ctx);
   const std::string dir = (out_dir && *out_dir) ? std::string(out_dir) + "/" : std::string();
+  uint64_t records = 0;
+  for (int j = 0; j < n_samples; ++j) records += src.total(j);
 
   uint64_t cap = 1024;
   while (cap < 2 * (records + (uint64_t)n_samples)) cap <<= 1;
   if (cap > (1ull << 32)) return set_error(KLSH_E_RANGE, "more than 2^31 distinct k-mers");
   const uint64_t mask = cap - 1;
-  constexpr uint64_t kChunkBytes = 64ull << 20;
   int rc = KLSH_OK;
-  uint64_t *tab = nullptr, *first = nullptr, *drep = nullptr, *dlut = nullptr, *keys_out = nullptr;
-  uint32_t *acc = nullptr, *dcnt = nullptr, *nvalid = nullptr, *lo = nullptr, *lo2 = nullptr;
+  uint64_t *tab = nullptr, *first = nullptr, *keys_out = nullptr, *dzero = nullptr;
+  uint32_t *acc = nullptr, *nvalid = nullptr, *lo = nullptr, *lo2 = nullptr;
   uint32_t *slots = nullptr, *slots2 = nullptr, *ws = nullptr;
   uint16_t* col = nullptr;
-  uint8_t* drec = nullptr;
-  std::vector<uint8_t> hrec(kChunkBytes);
   std::vector<uint64_t> base(n_samples + 1, hooks.ordinal_base);  // base[j]: sample j's first ordinal
   uint32_t kmap = 0;
   FILE *fh = nullptr, *fb = nullptr, *fl = nullptr;
   std::vector<float> coverage(n_samples, 0.0f);
-  uint64_t max_lut = 0, max_chunk_recs = 0;
-  for (const auto& db : dbs) {
-    max_lut = std::max<uint64_t>(max_lut, db.lut.size());
-    max_chunk_recs = std::max<uint64_t>(max_chunk_recs, kChunkBytes / db.params().rec_size + 1);
-  }
   KLSH_KHIP(hipMalloc((void**)&tab, cap * 8));
   KLSH_KHIP(hipMalloc((void**)&first, cap * 8));
   KLSH_KHIP(hipMalloc((void**)&acc, cap * 4));
-  KLSH_KHIP(hipMalloc((void**)&drec, kChunkBytes + 64));
-  KLSH_KHIP(hipMalloc((void**)&drep, max_chunk_recs * 8));
-  KLSH_KHIP(hipMalloc((void**)&dcnt, max_chunk_recs * 4));
-  KLSH_KHIP(hipMalloc((void**)&dlut, max_lut * 8));
   KLSH_KHIP(hipMalloc((void**)&nvalid, 64));
+  KLSH_KHIP(hipMalloc((void**)&dzero, 64));  // the all-A k-mer of a filtered sample
   KLSH_KHIP(hipMemsetAsync(tab, 0xFF, cap * 8, s));
   KLSH_KHIP(hipMemsetAsync(first, 0xFF, cap * 8, s));
 
-  // Stream sample j's records through decode + `per_chunk` (pass 1: union; pass 2: counts).
+  // Stream sample j's records through the source + the union (pass 0) / the counts (pass 1).
   for (int pass = 0; pass < 2; ++pass) {
     for (int j = 0; j < n_samples; ++j) {
-      const KmcDb& db = dbs[j];
-      const klsh::KmcParams kp = db.params();
-      KLSH_KHIP(hipMemcpyAsync(dlut, db.lut.data(), db.lut.size() * 8, hipMemcpyHostToDevice, s));
-      KLSH_KHIP(hipMemsetAsync(nvalid, 0, 4, s));
+      const uint64_t total = src.total(j), per_chunk = src.chunk(j);
       if (pass == 1) KLSH_KHIP(hipMemsetAsync(acc, 0, cap * 4, s));
-      FILE* f = fopen(db.suf.c_str(), "rb");
-      if (!f) {
-        rc = set_error(KLSH_E_ARG, ("cannot open " + db.suf).c_str());
-        goto done;
-      }
-      char mark[4];
-      if (fread(mark, 1, 4, f) != 4 || memcmp(mark, "KMCS", 4)) {
-        fclose(f);
-        rc = set_error(KLSH_E_ARG, (db.suf + ": bad marker").c_str());
-        goto done;
-      }
-      uint64_t per_chunk = kChunkBytes / kp.rec_size;  // what hrec / drec / drep / dcnt hold
-      if (hooks.chunk_records) per_chunk = std::min<uint64_t>(per_chunk, hooks.chunk_records);
-      float cov = 0.0f;
-      for (uint64_t r0 = 0; r0 < db.total; r0 += per_chunk) {
-        const uint64_t n = std::min<uint64_t>(per_chunk, db.total - r0);
-        const double tio = now_ms();
-        if (fread(hrec.data(), kp.rec_size, n, f) != n) {
-          fclose(f);
-          rc = set_error(KLSH_E_ARG, (db.suf + ": short file").c_str());
-          goto done;
-        }
-        local.io_ms += now_ms() - tio;
-        KLSH_KHIP(hipMemcpyAsync(drec, hrec.data(), n * kp.rec_size, hipMemcpyHostToDevice, s));
-        klsh::launch_kmc_decode(drec, n, r0, kp, dlut, db.lut.size(), drep, dcnt, nvalid, s);
-        if (pass == 0) ++hooks.decode_launches;
+      if ((rc = src.begin(j, pass, s))) goto done;
+      for (uint64_t r0 = 0; r0 < total; r0 += per_chunk) {
+        const uint64_t n = std::min<uint64_t>(per_chunk, total - r0);
+        const uint64_t* drep = nullptr;
+        const uint32_t* dcnt = nullptr;
+        if ((rc = src.feed(j, pass, r0, n, &drep, &dcnt, s))) goto done;
         if (pass == 0) klsh::launch_kmc_union(drep, n, base[j] + r0, tab, first, mask, s);
         else klsh::launch_kmc_count(drep, dcnt, n, tab, mask, acc, s);
         KLSH_KHIP(hipGetLastError());
-        if (pass == 1) {  // tot_coverage += log(cnt), float, file order (kmc_reader.cc:143)
-          for (uint64_t i = 0; i < n; ++i) {
-            const uint8_t* q = hrec.data() + i * kp.rec_size + kp.sufix_size;
-            uint32_t c = 0;
-            for (uint32_t b = 0; b < kp.counter_size; ++b) c |= (uint32_t)q[b] << (8 * b);
-            if (c >= db.min_count && (uint64_t)c <= db.max_count) cov += log((double)c);
-          }
-        }
-        KLSH_KHIP(hipStreamSynchronize(s));  // hrec is reused by the next read
+        src.fed(j, pass, n);
+        KLSH_KHIP(hipStreamSynchronize(s));  // the source reuses its buffers for the next chunk
       }
-      fclose(f);
-      local.records += db.total;
+      uint64_t nv = 0;
+      if ((rc = src.end(j, pass, &nv, &coverage[j], s))) goto done;
       if (pass == 0) {
-        uint32_t nv = 0;
-        KLSH_KHIP(hipMemcpy(&nv, nvalid, 4, hipMemcpyDeviceToHost));
         local.records_listed += nv;
         // fewer listed than the total: KmcRead's vector keeps default (all-A) k-mers at the end
-        if (nv < db.total) {
+        if (nv < total) {
           const uint64_t zero = 0;
-          KLSH_KHIP(hipMemcpyAsync(drep, &zero, 8, hipMemcpyHostToDevice, s));
-          klsh::launch_kmc_union(drep, 1, base[j] + db.total, tab, first, mask, s);
+          KLSH_KHIP(hipMemcpyAsync(dzero, &zero, 8, hipMemcpyHostToDevice, s));
+          klsh::launch_kmc_union(dzero, 1, base[j] + total, tab, first, mask, s);
           KLSH_KHIP(hipGetLastError());
           KLSH_KHIP(hipStreamSynchronize(s));
         }
-        base[j + 1] = base[j] + db.total + 1;
+        base[j + 1] = base[j] + total + 1;
       } else {
-        coverage[j] = cov;
         // this sample's column in output order (WriteHT, io/ioHT.cc:30-55)
         klsh::launch_kmc_emit(acc, slots, kmap, col, s);
         KLSH_KHIP(hipGetLastError());
@@ -565,10 +609,40 @@ done:
   if (fh) fclose(fh);
   if (fb) fclose(fb);
   if (fl) fclose(fl);
-  for (void* ptr : {(void*)tab, (void*)first, (void*)drep, (void*)dlut, (void*)keys_out, (void*)acc,
-                    (void*)dcnt, (void*)nvalid, (void*)lo, (void*)lo2, (void*)slots, (void*)slots2,
-                    (void*)ws, (void*)col, (void*)drec})
+  for (void* ptr : {(void*)tab, (void*)first, (void*)dzero, (void*)keys_out, (void*)acc,
+                    (void*)nvalid, (void*)lo, (void*)lo2, (void*)slots, (void*)slots2, (void*)ws,
+                    (void*)col})
     if (ptr) (void)hipFree(ptr);
+  return rc;
+}
+
+extern "C" int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, int n_samples,
+                                  int k, const char* out_dir, klsh_khtable_stats* st) {
+  if (!ctx || !kmc_names || n_samples <= 0) return set_error(KLSH_E_ARG, "bad argument");
+  if (k < 1 || k > 32) return set_error(KLSH_E_RANGE, "k must be in [1, 32] (Kmer::MAX_K)");
+  const double t_start = now_ms();
+  if (st && st->struct_size != sizeof(klsh_khtable_stats))
+    return set_error(KLSH_E_ARG, "klsh_khtable_stats.struct_size != sizeof: built against another klsh.h");
+  klsh_khtable_stats local{};
+  local.struct_size = sizeof(local);
+  klsh::KmcHooks& hooks = klsh::ctx_kmc(ctx);  // test hooks; what this call reaches
+  hooks.decode_launches = 0;
+  hooks.high_sort = 0;
+  hooks.first.clear();
+  std::vector<KmcDb> dbs(n_samples);
+  for (int j = 0; j < n_samples; ++j) {
+    if (!kmc_names[j] || !dbs[j].open(kmc_names[j]))
+      return set_error(KLSH_E_ARG, kmc_names[j] ? dbs[j].err.c_str() : "null database name");
+    if ((int)dbs[j].k != k)
+      return set_error(KLSH_E_ARG, (std::string(kmc_names[j]) + ": k-mer length differs from -K").c_str());
+  }
+  if (hipSetDevice(klsh::ctx_device(ctx)) != hipSuccess) return set_error(KLSH_E_HIP, "hipSetDevice");
+  int rc;
+  {
+    KmcFileSource src(dbs, hooks, local);
+    rc = src.alloc();
+    if (rc == KLSH_OK) rc = klsh::khtable_run(ctx, src, n_samples, k, out_dir, &local);
+  }
   local.total_ms = now_ms() - t_start;
   if (st) *st = local;
   return rc;

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "klsh_internal.h"
+#include "klsh_kmer.h"
 
 namespace klsh {
 
@@ -31,14 +32,6 @@ __device__ __forceinline__ uint64_t kmc_hash(uint64_t k) {  // murmur3 finalizer
   k *= 0xc4ceb9fe1a85ec53ull;
   k ^= k >> 33;
   return k;
-}
-
-__device__ __forceinline__ uint64_t reverse_bases(uint64_t v, int k) {
-  uint64_t x = v;
-  x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
-  x = ((x >> 4) & 0x0F0F0F0F0F0F0F0Full) | ((x & 0x0F0F0F0F0F0F0F0Full) << 4);
-  x = __builtin_bswap64(x);
-  return x >> (64 - 2 * k);
 }
 
 __global__ __launch_bounds__(256) void k_kmc_decode(const uint8_t* __restrict__ recs, uint64_t n,
@@ -66,10 +59,7 @@ __global__ __launch_bounds__(256) void k_kmc_decode(const uint8_t* __restrict__ 
     if (c >= kp.min_count && (uint64_t)c <= kp.max_count) {
       const uint64_t pre = lo & kp.prefix_mask;
       const uint64_t v = kp.p == 0 ? suf : (pre << (2 * (kp.k - kp.p))) | suf;  // s[0] on top
-      const uint64_t img = reverse_bases(v, kp.k);  // base i at bits 2i
-      // the twin's base i is the complement of base k-1-i: exactly the complemented KMC value
-      const uint64_t tw = ~v & (kp.k == 32 ? ~0ull : ((1ull << (2 * kp.k)) - 1ull));
-      key = __builtin_bswap64(img) < __builtin_bswap64(tw) ? img : tw;
+      key = kmc_value_rep(v, kp.k);  // klsh_kmer.h, shared with mode K's listing
       ++valid;
     }
     rep[i] = key;

@@ -1,12 +1,19 @@
-"""Throughput of the mode-E k-mer vote and the mode-B table build on one GPU (synthetic data).
+"""Throughput of the mode-E k-mer vote, the mode-B table build and the mode-K k-mer count on one
+GPU (synthetic data).
 
   python tools/bench_modes.py [--reads 2000000] [--kset 4000000] [--samples 8] [--kmers 4000000]
+                              [--kreads 1000000] [--kgenome 4000000] [--only K|B|E]
 
 Mode E: a FASTQ of random 150-bp reads, a third of them drawn from the sequence the k-mer set
 was cut from, through klsh_extract_fastq (host parse + GPU vote + writer); reports reads/s, k-mer
 probes/s of the vote kernel (HIP events) and the host parse time.
 Mode B: `samples` KMC1 databases of `kmers` random 31-mers each (half shared), through
-klsh_build_khtable; reports records/s.  Prints one JSON line per mode.
+klsh_build_khtable; reports records/s.
+Mode K: two samples of `kreads` 150-bp reads each, either strand of a `kgenome`-base genome pool
+with 1 % substitutions, through klsh_count_khtable (host parse + GPU count + table build);
+reports k-mer positions/s, the counting kernels' time against the host parse time, rehashes and
+the peak table size — once from plain FASTQ, once with a quarter of the reads gzipped, and once
+on the worst case for same-address atomics, poly-A reads.  Prints one JSON line per run.
 """
 from __future__ import annotations
 
@@ -115,18 +122,85 @@ def bench_khtable(engine, samples: int, n_kmers: int, k: int = 31) -> dict:
             "kmap_size": st["kmap_size"], "io_ms": st["io_ms"], "total_ms": st["total_ms"]}
 
 
+def _write_reads(path: str, seq: np.ndarray, gz: bool = False) -> None:
+    import gzip
+
+    n, L = seq.shape
+    qual = b"I" * L
+    with (gzip.open(path, "wb", compresslevel=1) if gz else open(path, "wb")) as f:
+        for a in range(0, n, 100000):
+            b = min(n, a + 100000)
+            f.write(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, seq[i].tobytes(), qual) for i in range(a, b)))
+
+
+def _count_run(engine, label: str, paths, k: int, count_min: int, tmp: str) -> dict:
+    engine.count_khtable(paths[:1], k, count_min, tmp)  # warm-up (page cache, code)
+    t = time.perf_counter()
+    st = engine.count_khtable(paths, k, count_min, tmp)
+    wall = time.perf_counter() - t
+    kms = st["kernel_ms"]
+    return {"mode": "K", "input": label,
+            "metric": "k-mer positions/s (FASTQ parse + GPU count + table build)",
+            "value": st["positions"] / wall, "k": k, "count_min": count_min, "samples": len(paths),
+            "reads": st["reads"], "positions": st["positions"], "distinct": st["distinct"],
+            "listed": st["listed"], "kmap_size": st["kmap_size"], "batches": st["batches"],
+            "rehashes": st["rehashes"], "peak_table_slots": engine.get_option("kcount_peak_slots"),
+            "kernel_ms": kms, "parse_ms": st["parse_ms"], "order_ms": st["order_ms"],
+            "total_ms": st["total_ms"],
+            "kernel_positions_per_s": st["positions"] / (kms / 1e3) if kms else None,
+            "kernel_share_of_total": kms / st["total_ms"] if st["total_ms"] else None}
+
+
+def bench_count(engine, n_reads: int, n_genome: int, k: int = 31, count_min: int = 2) -> list:
+    rng = np.random.default_rng(7)
+    pool = rng.integers(0, 4, size=n_genome, dtype=np.uint8)
+    L = 150
+    out = []
+    with tempfile.TemporaryDirectory(dir=os.environ.get("TMPDIR", "/tmp")) as tmp:
+        plain, mixed = [], []
+        for j in range(2):
+            starts = rng.integers(0, pool.size - L, size=n_reads)
+            codes = pool[starts[:, None] + np.arange(L)[None, :]]
+            flip = rng.integers(0, 2, size=n_reads).astype(bool)
+            codes[flip] = 3 - codes[flip, ::-1]
+            err = rng.random(codes.shape) < 0.01
+            codes[err] = rng.integers(0, 4, size=int(err.sum()), dtype=np.uint8)
+            seq = np.frombuffer(b"ACGT", np.uint8)[codes]
+            path = os.path.join(tmp, "s%d.fq" % j)
+            _write_reads(path, seq)
+            plain.append(path)
+            gz = os.path.join(tmp, "q%d.fq.gz" % j)
+            _write_reads(gz, seq[:n_reads // 4], gz=True)
+            mixed.append(gz)
+        out.append(_count_run(engine, "plain FASTQ", plain, k, count_min, tmp))
+        out.append(_count_run(engine, "gzip FASTQ (a quarter of the reads)", mixed, k, count_min, tmp))
+        # worst case for same-address atomics: every window of every read is the same k-mer
+        poly = os.path.join(tmp, "polyA.fq")
+        _write_reads(poly, np.full((max(1, n_reads // 400), 60000), ord("A"), np.uint8))
+        out.append(_count_run(engine, "poly-A reads of 60000 bases", [poly], k, count_min, tmp))
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=2000000)
     ap.add_argument("--kset", type=int, default=4000000)
     ap.add_argument("--samples", type=int, default=8)
     ap.add_argument("--kmers", type=int, default=4000000)
+    ap.add_argument("--kreads", type=int, default=1000000)
+    ap.add_argument("--kgenome", type=int, default=4000000)
+    ap.add_argument("--only", choices=("K", "B", "E"), default=None)
     a = ap.parse_args()
     from kmerlsh_amd import _native
 
     with _native.Engine(0) as eng:
-        print(json.dumps(bench_extract(eng, a.reads, a.kset)), flush=True)
-        print(json.dumps(bench_khtable(eng, a.samples, a.kmers)), flush=True)
+        if a.only in (None, "E"):
+            print(json.dumps(bench_extract(eng, a.reads, a.kset)), flush=True)
+        if a.only in (None, "B"):
+            print(json.dumps(bench_khtable(eng, a.samples, a.kmers)), flush=True)
+        if a.only in (None, "K"):
+            for row in bench_count(eng, a.kreads, a.kgenome):
+                print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":
