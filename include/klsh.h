@@ -402,6 +402,44 @@ int klsh_count_khtable(klsh_ctx* ctx, const char* const* fastq_paths, int n_samp
 int klsh_kcount_listing(klsh_ctx* ctx, int sample, uint64_t* kmc_values, uint32_t* counts,
                         uint64_t* n);
 
+/* Mode K with its databases: what klsh_count_khtable does, and each sample's listing written as
+ * the KMC database the reference's `kmc` run would leave for mode B (the listing is written from
+ * the device right after the sample is counted; no FASTQ file is read twice).  db_names[j] is
+ * sample j's database path without extension (the sample lists' second column): <name>.kmc_pre
+ * and <name>.kmc_suf, KMC1 layout (version 0), both strands, 2-byte counters (-cs65535):
+ *   .kmc_suf  "KMCS", the records in ascending KMC value — (k - p) / 4 suffix bytes (the value's
+ *             low 2 (k - p) bits, most significant byte first), then the counter in 2 bytes,
+ *             little-endian — "KMCS"
+ *   .kmc_pre  "KMCP", 4^p little-endian uint64 (entry q: the records whose prefix,
+ *             value >> 2 (k - p), is below q), the header of five uint64 (k; 2 | p << 32;
+ *             max(count_min, 1) | 65535 << 32; the record count; 0), the uint32 40, "KMCP"
+ * p, the prefix length, is the one in [0, min(k, 15)] with (k - p) % 4 == 0 that makes the two
+ * files smallest, 8 * 4^p + records * ((k - p) / 4 + 2) bytes, the smaller p on a tie.
+ * out_dir NULL: the databases only (the reference's `-M K --only`): no table is built, none of its
+ * three files is written, kmap_size stays 0, and a listing is freed once its database is written.
+ * out_dir not NULL ("" = the current directory): the databases, then the table exactly as
+ * klsh_count_khtable.  db_names NULL: klsh_count_khtable.  Both NULL: KLSH_E_ARG.
+ * Before any device work, KLSH_E_ARG for a NULL or repeated entry of db_names, a database file
+ * that cannot be opened for writing, and a forced prefix length that k does not allow.  A failed
+ * write returns KLSH_E_ARG after removing that sample's two files; the databases of the samples
+ * before it stay.  stats and db_stats may be NULL.
+ * Context options (test hooks; the defaults are the product's behaviour):
+ *   "kcount_db_prefix"         -1 (default) = p by the size rule, otherwise p itself
+ *   "kcount_db_chunk_records"  records packed, copied and written at a time (0 = default, 2^22)
+ *   read-only, of the context's last call: "kcount_db_chunks" (record chunks packed: per sample,
+ *   its records over the chunk size, rounded up) and "kcount_db_prefix_used" (p of the last
+ *   database written; -1 = none). */
+typedef struct klsh_kmcdb_stats {
+  uint64_t struct_size; /* in: sizeof(klsh_kmcdb_stats) */
+  uint64_t databases, records, bytes /* of both files, all samples */, chunks;
+  uint32_t prefix_len_min, prefix_len_max;
+  double pack_ms;  /* HIP-event time of the record-packing and prefix-table kernels */
+  double write_ms; /* host file writes */
+} klsh_kmcdb_stats;
+int klsh_count_kmc(klsh_ctx* ctx, const char* const* fastq_paths, const char* const* db_names,
+                   int n_samples, int k, int count_min, const char* out_dir,
+                   klsh_kcount_stats* stats, klsh_kmcdb_stats* db_stats);
+
 /* ---- synthetic workload (klsh-synth v1) ------------------------------------ */
 /* Host-side, deterministic on any machine (integer hashing + glibc exp/log/sqrt): fills counts
  * (sample-major d x n uint16, the kmer_count.bin layout) and coverage[d] = sum over i of ln(c)

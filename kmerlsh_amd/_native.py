@@ -37,7 +37,7 @@ EXPORTED = (
     "klsh_fastq_next", "klsh_fastq_close", "klsh_kset_create", "klsh_kset_destroy",
     "klsh_check_reads", "klsh_extract_fastq", "klsh_build_khtable", "klsh_cuckoo_order",
     "klsh_kmc_info", "klsh_khtable_first", "klsh_bucket_runs", "klsh_row_state",
-    "klsh_count_khtable", "klsh_kcount_listing",
+    "klsh_count_khtable", "klsh_kcount_listing", "klsh_count_kmc",
 )
 
 
@@ -137,6 +137,20 @@ class KlshKcountStats(_Sized):
     ]
 
 
+class KlshKmcdbStats(_Sized):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("databases", ctypes.c_uint64),
+        ("records", ctypes.c_uint64),
+        ("bytes", ctypes.c_uint64),
+        ("chunks", ctypes.c_uint64),
+        ("prefix_len_min", ctypes.c_uint32),
+        ("prefix_len_max", ctypes.c_uint32),
+        ("pack_ms", ctypes.c_double),
+        ("write_ms", ctypes.c_double),
+    ]
+
+
 class KlshKhtableStats(_Sized):
     _fields_ = [
         ("struct_size", ctypes.c_uint64),
@@ -224,6 +238,9 @@ def load_library() -> ctypes.CDLL:
         "klsh_count_khtable": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_char_p, _P]),
         "klsh_kcount_listing": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, _u64p]),
+        "klsh_count_kmc": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p),
+                                          ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_char_p, _P, _P]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("KLSH_LIB") and not hasattr(lib, name):
@@ -522,6 +539,26 @@ class Engine:
                                             os.fspath(out_dir).encode(), ctypes.byref(st)),
                "klsh_count_khtable")
         return st.as_dict()
+
+    def count_kmc(self, fastq_paths, db_names, k: int, count_min: int = 2,
+                  out_dir=None) -> tuple[dict, dict]:
+        """Mode K with its databases: sample j's listing written as the KMC database
+        db_names[j] (.kmc_pre / .kmc_suf, what build_khtable reads), and, unless out_dir is None,
+        the three table files in out_dir as count_khtable writes them.  db_names None: only the
+        table.  Returns (counting statistics, database statistics)."""
+        arr = (ctypes.c_char_p * len(fastq_paths))(*[os.fspath(n).encode() for n in fastq_paths])
+        dbs = None
+        if db_names is not None:
+            if len(db_names) != len(fastq_paths):
+                raise ValueError("one database name per FASTQ file")
+            # None stays a NULL entry (the library refuses it)
+            dbs = (ctypes.c_char_p * len(db_names))(
+                *[None if n is None else os.fspath(n).encode() for n in db_names])
+        st, dst = KlshKcountStats(), KlshKmcdbStats()
+        _check(self._lib.klsh_count_kmc(self._ctx, arr, dbs, len(fastq_paths), k, count_min,
+                                        None if out_dir is None else os.fspath(out_dir).encode(),
+                                        ctypes.byref(st), ctypes.byref(dst)), "klsh_count_kmc")
+        return st.as_dict(), dst.as_dict()
 
     def kcount_listing(self, sample: int) -> tuple[np.ndarray, np.ndarray]:
         """Sample `sample`'s listing of the last count_khtable made with option

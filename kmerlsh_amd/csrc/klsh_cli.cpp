@@ -12,17 +12,23 @@
 //           kmer_count.bin, kmer_count.log (io/ioHT.cc:83-199 with existing databases).
 //   mode K  counts the k-mers of the FASTQ files named in the lists' first column on the GPU (what
 //           the reference runs `kmc -k<K> -r -cs65535 -ci<C>` for, io/ioHT.cc:100-103) and writes
-//           the same three files; no KMC database is written and the second column is unused.
+//           the same three files.  With --kmc-db each sample's listing is also written as the
+//           KMC database named in the second column (.kmc_pre / .kmc_suf, what mode B reads),
+//           which is what the reference's mode K leaves behind; with --kmc-db-only (-M K --only)
+//           the databases alone, the reference's own -M K --only.  Without either flag no
+//           database is written and the second column is unused.
 // Mode selection as the reference's (app/kmerLSH.cc:234-275): -M E [--only] extracts only,
 // -M C --only clusters only, -M C clusters and then extracts, -M B --only builds the table only,
 // -M B builds, clusters and extracts, -M K --only counts and writes the table only, -M K or no -M
 // (the reference's default: everything) counts, clusters and extracts.
 //   kmerLSH -a A.txt -b B.txt [-o A -p B] [-I iters] [-N min_sim] [-K k] [-C count_min] [-S size]
 //           [-P pval] [-V vote] [-F file] [-M K|B|C|E] [--only] [--verbose] [--seed S] [--device D]
+//           [--kmc-db | --kmc-db-only]
 // -C is the smallest count a k-mer is listed with (kmc's -ci, default 2); -X is accepted and
 // ignored (kmc's memory limit).
-// Additions: --seed (the reference seeds from std::random_device; SURVEY.md §8(c) convention)
-// and --device.  -T is accepted and ignored (results never depend on a thread count).
+// Additions: --seed (the reference seeds from std::random_device; SURVEY.md §8(c) convention),
+// --device, and --kmc-db / --kmc-db-only (usage errors, exit 2, where mode K does not run;
+// --kmc-db-only also anywhere but -M K --only).  -T is accepted and ignored (results never depend on a thread count).
 // The init pass keeps the reference's 1e8-row batching and re-cluster passes
 // (app/kmerLSH.cc:278-430); its tmp-file round trip is lossless and stays in memory.
 #include <getopt.h>
@@ -166,16 +172,37 @@ int run_build(klsh_ctx* ctx, const char* in1, const char* in2, int k, bool verbo
 }
 
 // Mode K (buildKHtable with kmc = true): the FASTQ files of the lists' first column counted on the
-// GPU -> kmer_set.hex / kmer_count.bin / kmer_count.log in the current directory.
-int run_count(klsh_ctx* ctx, const char* in1, const char* in2, int k, int count_min, bool verbose) {
+// GPU -> kmer_set.hex / kmer_count.bin / kmer_count.log in the current directory.  db: 0 = no
+// database, 1 = also each sample's KMC database under the name in the second column, 2 = the
+// databases and no table.
+int run_count(klsh_ctx* ctx, const char* in1, const char* in2, int k, int count_min, bool verbose,
+              int db) {
   std::vector<std::string> names = sample_paths(in1, 0), n2 = sample_paths(in2, 0);
   names.insert(names.end(), n2.begin(), n2.end());
   std::vector<const char*> ptrs;
   for (const auto& n : names) ptrs.push_back(n.c_str());
   klsh_kcount_stats st{};
   st.struct_size = sizeof(st);
-  check(klsh_count_khtable(ctx, ptrs.data(), (int)ptrs.size(), k, count_min, "", &st),
-        "klsh_count_khtable");
+  if (db) {
+    std::vector<std::string> dbs = sample_paths(in1, 1), d2 = sample_paths(in2, 1);
+    dbs.insert(dbs.end(), d2.begin(), d2.end());
+    std::vector<const char*> dptrs;
+    for (const auto& n : dbs) dptrs.push_back(n.c_str());
+    klsh_kmcdb_stats dst{};
+    dst.struct_size = sizeof(dst);
+    check(klsh_count_kmc(ctx, ptrs.data(), dptrs.data(), (int)ptrs.size(), k, count_min,
+                         db == 2 ? nullptr : "", &st, &dst),
+          "klsh_count_kmc");
+    if (verbose)
+      printf("KMC databases: %llu, %llu records, %llu bytes in %llu chunks, prefix length %u..%u "
+             "(packing kernels %.1f ms, writing %.1f ms)\n",
+             (unsigned long long)dst.databases, (unsigned long long)dst.records,
+             (unsigned long long)dst.bytes, (unsigned long long)dst.chunks, dst.prefix_len_min,
+             dst.prefix_len_max, dst.pack_ms, dst.write_ms);
+  } else {
+    check(klsh_count_khtable(ctx, ptrs.data(), (int)ptrs.size(), k, count_min, "", &st),
+          "klsh_count_khtable");
+  }
   if (verbose)
     printf("k-mer table: %llu k-mers (%llu listed of %llu distinct, %llu k-mer positions, %llu reads "
            "of %zu samples; %.1f ms, counting kernels %.1f ms, parsing %.1f ms, %llu rehashes)\n",
@@ -319,7 +346,7 @@ int main(int argc, char** argv) {
   const char *in1 = nullptr, *in2 = nullptr;
   std::string out = "clustering_result.txt", mode, out1, out2;
   int iters = 100, verbose = 0, only = 0, device = 0, kmer_k = 23, size_thresh = 500000,
-      count_min = 2;
+      count_min = 2, kmc_db = 0;
   float min_sim = 0.80f, pval = 0.01f, vote = 0.5f;
   uint32_t seed = 12345u;
   static struct option lo[] = {{"verbose", no_argument, 0, 1},
@@ -339,6 +366,8 @@ int main(int argc, char** argv) {
                                {"clust_file_name", required_argument, 0, 'F'},
                                {"mode", required_argument, 0, 'M'},
                                {"tmp_dir", required_argument, 0, 5},
+                               {"kmc-db", no_argument, 0, 6},
+                               {"kmc-db-only", no_argument, 0, 7},
                                {0, 0, 0, 0}};
   int c;
   while ((c = getopt_long(argc, argv, "o:p:a:b:H:I:N:X:C:T:K:S:P:V:F:M:", lo, nullptr)) != -1) {
@@ -347,6 +376,8 @@ int main(int argc, char** argv) {
       case 2: only = 1; break;
       case 3: seed = (uint32_t)strtoul(optarg, nullptr, 10); break;
       case 4: device = atoi(optarg); break;
+      case 6: kmc_db |= 1; break;
+      case 7: kmc_db |= 2; break;
       case 'o': out1 = optarg; break;
       case 'p': out2 = optarg; break;
       case 'K': kmer_k = atoi(optarg); break;
@@ -365,7 +396,8 @@ int main(int argc, char** argv) {
   }
   if (argc < 2 || !in1 || !in2) {
     fprintf(stderr, "usage: kmerLSH -a A.txt -b B.txt [-o A -p B] [-I iters] [-N min_sim] [-K k] "
-                    "[-C count_min] [-S size] [-P pval] [-V vote] [-F out] [-M K|B|C|E] [--only]\n");
+                    "[-C count_min] [-S size] [-P pval] [-V vote] [-F out] [-M K|B|C|E] [--only] "
+                    "[--kmc-db | --kmc-db-only]\n");
     return 1;
   }
   if (!mode.empty() && mode != "K" && mode != "B" && mode != "C" && mode != "E") {
@@ -378,6 +410,15 @@ int main(int argc, char** argv) {
   const bool building = mode == "B" || counting;
   const bool clustering = mode == "C" || (building && !(only && !mode.empty()));
   const bool extracting = mode == "E" || !only || mode.empty();  // --only without -M names no mode
+  if ((kmc_db & 2) && (kmc_db & 1 || mode != "K" || !only)) {
+    fprintf(stderr, "kmerLSH: --kmc-db-only goes with -M K --only, and without --kmc-db\n");
+    return 2;
+  }
+  if (kmc_db && !counting) {
+    fprintf(stderr, "kmerLSH: --kmc-db writes the databases that mode K counts; -M %s does not "
+                    "run mode K\n", mode.c_str());
+    return 2;
+  }
   const auto t0 = std::chrono::steady_clock::now();
   const int d = count_lines(in1) + count_lines(in2);
   if (building) {
@@ -387,7 +428,7 @@ int main(int argc, char** argv) {
       fprintf(stderr, "kmerLSH: %s\n", klsh_last_error());
       return 2;
     }
-    const int rc = counting ? run_count(ctx, in1, in2, kmer_k, count_min, verbose)
+    const int rc = counting ? run_count(ctx, in1, in2, kmer_k, count_min, verbose, kmc_db)
                             : run_build(ctx, in1, in2, kmer_k, verbose);
     klsh_destroy(ctx);
     if (rc || (!clustering && !extracting)) return rc;

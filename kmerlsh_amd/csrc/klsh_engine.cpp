@@ -2016,6 +2016,16 @@ int klsh_set_option(klsh_ctx* ctx, const char* name, int64_t value) {
     ctx->kcount.table_slots = (uint64_t)value;
     return 0;
   }
+  if (n == "kcount_db_prefix") {
+    if (value < -1 || value > 15) return fail(KLSH_E_ARG, "kcount_db_prefix must be in [-1, 15]");
+    ctx->kcount.db_prefix = (int)value;
+    return 0;
+  }
+  if (n == "kcount_db_chunk_records") {
+    if (value < 0) return fail(KLSH_E_ARG, "kcount_db_chunk_records must be >= 0");
+    ctx->kcount.db_chunk_records = (uint64_t)value;
+    return 0;
+  }
   if (n == "kcount_keep_listing") {
     if (!value) {
       std::vector<std::vector<uint64_t>>().swap(ctx->kcount.values);
@@ -2091,6 +2101,10 @@ int klsh_get_option(klsh_ctx* ctx, const char* name, int64_t* value) {
   else if (n == "kcount_rehashes") *value = (int64_t)ctx->kcount.rehashes;
   else if (n == "kcount_peak_slots") *value = (int64_t)ctx->kcount.peak_slots;
   else if (n == "kcount_window") *value = (int64_t)klsh::kKcountWindow;
+  else if (n == "kcount_db_prefix") *value = ctx->kcount.db_prefix;
+  else if (n == "kcount_db_chunk_records") *value = (int64_t)ctx->kcount.db_chunk_records;
+  else if (n == "kcount_db_chunks") *value = (int64_t)ctx->kcount.db_chunks;
+  else if (n == "kcount_db_prefix_used") *value = ctx->kcount.db_prefix_used;
   else if (n == "h16_grid") *value = ctx->pw.h16_grid;
   else if (n == "h16_segcap") *value = ctx->pw.segcap;
   else if (n == "wide_grid") *value = ctx->pw.wide_grid;

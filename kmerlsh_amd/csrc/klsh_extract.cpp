@@ -496,8 +496,11 @@ struct FastqReader {
     qual.resize(q0);
   }
   // up to max_reads records (or until ~max_bases sequence bytes): FastqFile::read
-  // (utils/fastq.cc:54-67) with larger parts — part boundaries change nothing downstream
-  uint64_t batch(uint64_t max_reads, uint64_t max_bases) {
+  // (utils/fastq.cc:54-67) with larger parts — part boundaries change nothing downstream.
+  // On a 64-byte boundary: next()'s byte loops are inlined here, and their speed moved with the
+  // function's offset inside a cache line (mode K's parse of 2 x 10^6 reads: 660 ms at offset 0,
+  // 725 ms at offset 16, which is where growth of the objects linked before this one had put it).
+  __attribute__((aligned(64))) uint64_t batch(uint64_t max_reads, uint64_t max_bases) {
     seq.clear();
     name.clear();
     qual.clear();

@@ -522,16 +522,31 @@ void launch_kcount_hi(const uint64_t* keys, const uint32_t* slots, uint64_t n, u
 // the listing in `order`: KMC value, canonical Kmer image, min(count, 65535)
 void launch_kcount_emit(const uint64_t* keys, const uint32_t* cnt, const uint32_t* order, uint64_t n,
                         int k, uint64_t* val, uint64_t* rep, uint32_t* out_cnt, hipStream_t s);
+// A listing as a KMC1-layout database (klsh_count_kmc): records [r0, r0 + m) of (val, cnt) as
+// .kmc_suf record bytes in out[0, m * (sufix_size + 2)) — sufix_size = (k - p) / 4 big-endian
+// suffix bytes, then the 2-byte little-endian counter; out 4-byte aligned
+constexpr uint32_t kKmcdbMaxRec = 10;  // k = 32, p = 0: 8 suffix bytes + the counter
+void launch_kmcdb_pack(const uint64_t* val, const uint32_t* cnt, uint64_t r0, uint64_t m,
+                       uint32_t sufix_size, uint8_t* out, hipStream_t s);
+// lut[i] = records whose prefix (val >> 2 (k - p)) is below q0 + i, for i < mq; val: n ascending
+void launch_kmcdb_lut(const uint64_t* val, uint64_t n, uint64_t q0, uint64_t mq, int k, int p,
+                      uint64_t* lut, hipStream_t s);
 
-// klsh_count_khtable's test hooks and what its last call on the context reached (options
-// "kcount_batch_reads", "kcount_table_slots", "kcount_keep_listing"; read-only "kcount_batches",
-// "kcount_rehashes", "kcount_peak_slots", "kcount_window"; klsh_kcount_listing).
+// klsh_count_khtable's / klsh_count_kmc's test hooks and what the last call on the context
+// reached (options "kcount_batch_reads", "kcount_table_slots", "kcount_keep_listing",
+// "kcount_db_prefix", "kcount_db_chunk_records"; read-only "kcount_batches", "kcount_rehashes",
+// "kcount_peak_slots", "kcount_window", "kcount_db_chunks", "kcount_db_prefix_used";
+// klsh_kcount_listing).
 struct KcountHooks {
   uint64_t batch_reads = 0;   // reads per batch (0 = 2^18)
   uint64_t table_slots = 0;   // a sample's initial table (0 = 2^22 slots)
   bool keep_listing = false;  // keep the per-sample listings of the next calls
   uint64_t batches = 0, rehashes = 0;
   uint64_t peak_slots = 0;    // the largest sample table of the last call
+  int db_prefix = -1;              // a database's LUT prefix length (-1 = the size rule)
+  uint64_t db_chunk_records = 0;   // records per .kmc_suf chunk (0 = 2^22)
+  uint64_t db_chunks = 0;          // k_kmcdb_pack launches of the last call
+  int db_prefix_used = -1;         // the prefix length of its last database (-1 = none written)
   std::vector<std::vector<uint64_t>> values;  // per sample: the listed KMC values, ascending
   std::vector<std::vector<uint32_t>> counts;
 };

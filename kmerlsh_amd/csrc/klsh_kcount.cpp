@@ -10,11 +10,16 @@
 // word): the listing of a KMC1-layout database, the convention of DESIGN.md §8.  The listings
 // stay on the device until every sample is counted; the table build of mode B (klsh::khtable_run,
 // klsh_kmc.cpp) then streams them as it streams decoded database records.
+//
+// klsh_count_kmc also writes what the reference's `kmc` run leaves: right after a sample is
+// listed, while its values are still in the counter's buffer, the listing goes out as the
+// sample's KMC1-layout database (DbWriter below; k_kmcdb_pack / k_kmcdb_lut).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <string>
@@ -76,6 +81,183 @@ class ListingSource : public klsh::KhSource {
   }
 };
 
+// The prefix length of a database of n records: p in [0, min(k, 15)] with (k - p) % 4 == 0 that
+// makes .kmc_pre + .kmc_suf smallest, the smaller p on a tie.
+bool db_prefix_ok(int k, int p) { return p >= 0 && p <= k && p <= 15 && (k - p) % 4 == 0; }
+int db_prefix_length(int k, uint64_t n) {
+  int best = -1;
+  uint64_t best_bytes = 0;
+  for (int p = k % 4; db_prefix_ok(k, p); p += 4) {
+    const uint64_t bytes = (8ull << (2 * p)) + n * (uint64_t)((k - p) / 4 + 2);
+    if (best < 0 || bytes < best_bytes) best = p, best_bytes = bytes;
+  }
+  return best;
+}
+
+// A sample's listing, still on the device, written as its KMC1-layout database (klsh.h,
+// klsh_count_kmc).  One device buffer and two pinned ones: while the host writes a chunk from one
+// pinned buffer, the next chunk is packed and copied into the other.  The prefix table goes
+// through the same buffers, a buffer of entries at a time.
+class DbWriter {
+ public:
+  DbWriter(klsh_ctx* ctx, int k, uint32_t count_min, klsh_kmcdb_stats& st)
+      : hooks_(klsh::ctx_kcount(ctx)), s_(klsh::ctx_stream(ctx)), k_(k), count_min_(count_min),
+        st_(st) {}
+  ~DbWriter() {
+    (void)hipStreamSynchronize(s_);  // no copy into the pinned buffers stays queued
+    if (dev_) (void)hipFree(dev_);
+    for (auto& b : buf_) {
+      if (b.host) (void)hipHostFree(b.host);
+      for (hipEvent_t e : {b.e0, b.e1, b.done})
+        if (e) (void)hipEventDestroy(e);
+    }
+  }
+  int init() {
+    for (auto& b : buf_) {
+      KLSH_CRET(hipEventCreate(&b.e0));
+      KLSH_CRET(hipEventCreate(&b.e1));
+      KLSH_CRET(hipEventCreate(&b.done));
+    }
+    return KLSH_OK;
+  }
+
+  // the n records (val ascending, cnt) as <name>.kmc_pre / <name>.kmc_suf; on a failure neither
+  // file is left
+  int write(const std::string& name, const uint64_t* val, const uint32_t* cnt, uint64_t n) {
+    const int p = hooks_.db_prefix >= 0 ? hooks_.db_prefix : db_prefix_length(k_, n);
+    const std::string pre = name + ".kmc_pre", suf = name + ".kmc_suf";
+    FILE* fs = fopen(suf.c_str(), "wb");
+    FILE* fp = fs ? fopen(pre.c_str(), "wb") : nullptr;
+    int rc = fp ? KLSH_OK : set_error(KLSH_E_ARG, ("cannot write " + (fs ? pre : suf)).c_str());
+    uint64_t bytes = 0;
+    if (rc == KLSH_OK) rc = records(fs, suf, val, cnt, n, p, &bytes);
+    if (rc == KLSH_OK) rc = prefix(fp, pre, val, n, p, &bytes);
+    const double tw = now_ms();
+    if (fs && fclose(fs) != 0 && rc == KLSH_OK) rc = set_error(KLSH_E_ARG, (suf + ": write failed").c_str());
+    if (fp && fclose(fp) != 0 && rc == KLSH_OK) rc = set_error(KLSH_E_ARG, (pre + ": write failed").c_str());
+    st_.write_ms += now_ms() - tw;
+    if (rc != KLSH_OK) {
+      (void)hipStreamSynchronize(s_);
+      if (fs) (void)remove(suf.c_str());
+      if (fp) (void)remove(pre.c_str());
+      return rc;
+    }
+    st_.prefix_len_min = st_.databases ? std::min<uint32_t>(st_.prefix_len_min, (uint32_t)p) : (uint32_t)p;
+    st_.prefix_len_max = std::max<uint32_t>(st_.prefix_len_max, (uint32_t)p);
+    st_.databases += 1;
+    st_.records += n;
+    st_.bytes += bytes;
+    hooks_.db_prefix_used = p;
+    return KLSH_OK;
+  }
+
+ private:
+  struct Buf {
+    uint8_t* host = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr, done = nullptr;  // around the kernel; after the copy
+  } buf_[2];
+  klsh::KcountHooks& hooks_;
+  hipStream_t s_;
+  int k_;
+  uint32_t count_min_;
+  klsh_kmcdb_stats& st_;
+  uint8_t* dev_ = nullptr;
+  uint64_t cap_ = 0;  // bytes of dev_ and of each pinned buffer
+  static constexpr uint64_t kChunkRecords = 1ull << 22, kMinBytes = 4ull << 20;
+
+  int reserve(uint64_t bytes) {
+    if (bytes <= cap_) return KLSH_OK;
+    KLSH_CRET(hipStreamSynchronize(s_));
+    if (dev_) (void)hipFree(dev_);
+    dev_ = nullptr;
+    cap_ = 0;
+    for (auto& b : buf_) {
+      if (b.host) (void)hipHostFree(b.host);
+      b.host = nullptr;
+    }
+    KLSH_CRET(hipMalloc((void**)&dev_, bytes));
+    for (auto& b : buf_) KLSH_CRET(hipHostMalloc((void**)&b.host, bytes, hipHostMallocDefault));
+    cap_ = bytes;
+    return KLSH_OK;
+  }
+  int put(FILE* f, const std::string& path, const void* data, uint64_t bytes, uint64_t* total) {
+    const double tw = now_ms();
+    const bool ok = bytes == 0 || fwrite(data, 1, bytes, f) == bytes;
+    st_.write_ms += now_ms() - tw;
+    *total += bytes;
+    return ok ? KLSH_OK : set_error(KLSH_E_ARG, (path + ": write failed").c_str());
+  }
+  // a piece finished on the device: its kernel time, then its bytes to the file
+  int drain(Buf& b, FILE* f, const std::string& path, uint64_t bytes, uint64_t* total) {
+    KLSH_CRET(hipEventSynchronize(b.done));
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, b.e0, b.e1);
+    st_.pack_ms += ms;
+    return put(f, path, b.host, bytes, total);
+  }
+
+  // "KMCS", the records chunk by chunk, "KMCS"
+  int records(FILE* f, const std::string& path, const uint64_t* val, const uint32_t* cnt,
+              uint64_t n, int p, uint64_t* total) {
+    const uint32_t sufix = (uint32_t)(k_ - p) / 4u, rec = sufix + 2u;
+    const uint64_t per = hooks_.db_chunk_records ? hooks_.db_chunk_records : kChunkRecords;
+    int rc = put(f, path, "KMCS", 4, total);
+    if (rc) return rc;
+    if ((rc = reserve(std::max<uint64_t>(std::min<uint64_t>(per, n) * rec, kMinBytes)))) return rc;
+    auto start = [&](uint64_t r0) {  // chunk r0 / per packed and on its way to its pinned buffer
+      Buf& b = buf_[(r0 / per) & 1];
+      const uint64_t m = std::min<uint64_t>(per, n - r0);
+      KLSH_CRET(hipEventRecord(b.e0, s_));
+      klsh::launch_kmcdb_pack(val, cnt, r0, m, sufix, dev_, s_);
+      KLSH_CRET(hipGetLastError());
+      KLSH_CRET(hipEventRecord(b.e1, s_));
+      KLSH_CRET(hipMemcpyAsync(b.host, dev_, m * rec, hipMemcpyDeviceToHost, s_));
+      KLSH_CRET(hipEventRecord(b.done, s_));
+      hooks_.db_chunks += 1;
+      st_.chunks += 1;
+      return (int)KLSH_OK;
+    };
+    if (n && (rc = start(0))) return rc;
+    for (uint64_t r0 = 0; r0 < n; r0 += per) {
+      if (r0 + per < n && (rc = start(r0 + per))) return rc;
+      if ((rc = drain(buf_[(r0 / per) & 1], f, path, std::min<uint64_t>(per, n - r0) * rec, total)))
+        return rc;
+    }
+    return put(f, path, "KMCS", 4, total);
+  }
+
+  // "KMCP", the prefix table, the header, its size, "KMCP"
+  int prefix(FILE* f, const std::string& path, const uint64_t* val, uint64_t n, int p,
+             uint64_t* total) {
+    const uint64_t entries = 1ull << (2 * p), per = cap_ / 8;
+    int rc = put(f, path, "KMCP", 4, total);
+    if (rc) return rc;
+    auto start = [&](uint64_t q0) {
+      Buf& b = buf_[(q0 / per) & 1];
+      const uint64_t mq = std::min<uint64_t>(per, entries - q0);
+      KLSH_CRET(hipEventRecord(b.e0, s_));
+      klsh::launch_kmcdb_lut(val, n, q0, mq, k_, p, reinterpret_cast<uint64_t*>(dev_), s_);
+      KLSH_CRET(hipGetLastError());
+      KLSH_CRET(hipEventRecord(b.e1, s_));
+      KLSH_CRET(hipMemcpyAsync(b.host, dev_, mq * 8, hipMemcpyDeviceToHost, s_));
+      KLSH_CRET(hipEventRecord(b.done, s_));
+      return (int)KLSH_OK;
+    };
+    if ((rc = start(0))) return rc;
+    for (uint64_t q0 = 0; q0 < entries; q0 += per) {
+      if (q0 + per < entries && (rc = start(q0 + per))) return rc;
+      if ((rc = drain(buf_[(q0 / per) & 1], f, path, std::min<uint64_t>(per, entries - q0) * 8, total)))
+        return rc;
+    }
+    const uint64_t header[5] = {(uint64_t)k_, 2ull | ((uint64_t)p << 32),
+                                (uint64_t)count_min_ | (65535ull << 32), n, 0ull};
+    const uint32_t header_size = sizeof(header);
+    if ((rc = put(f, path, header, sizeof(header), total))) return rc;
+    if ((rc = put(f, path, &header_size, 4, total))) return rc;
+    return put(f, path, "KMCP", 4, total);
+  }
+};
+
 // The counting of one call: the sample table, the two batch slots, the sort buffers.
 class Counter {
  public:
@@ -120,6 +302,8 @@ class Counter {
     if (rc) return rc;
     return list(out, keep_val, keep_cnt);
   }
+  // the KMC values of the last sample's listing (device), until the next sample is listed
+  const uint64_t* values() const { return val_; }
 
  private:
   struct Slot {
@@ -336,19 +520,29 @@ extern "C" int klsh_kcount_listing(klsh_ctx* ctx, int sample, uint64_t* kmc_valu
   return KLSH_OK;
 }
 
-extern "C" int klsh_count_khtable(klsh_ctx* ctx, const char* const* fastq_paths, int n_samples,
-                                  int k, int count_min, const char* out_dir,
-                                  klsh_kcount_stats* st) {
+namespace {
+
+// klsh_count_khtable (db_names == nullptr) and klsh_count_kmc: every sample counted and listed,
+// its database written while its values are still on the device, then (table) the table build.
+int count_run(klsh_ctx* ctx, const char* const* fastq_paths, const char* const* db_names,
+              int n_samples, int k, int count_min, const char* out_dir, bool table,
+              klsh_kcount_stats* st, klsh_kmcdb_stats* dst) {
   if (!ctx || !fastq_paths || n_samples <= 0) return set_error(KLSH_E_ARG, "bad argument");
   if (k < 1 || k > 32) return set_error(KLSH_E_RANGE, "k must be in [1, 32] (Kmer::MAX_K)");
   const double t_start = now_ms();
   if (st && st->struct_size != sizeof(klsh_kcount_stats))
     return set_error(KLSH_E_ARG, "klsh_kcount_stats.struct_size != sizeof: built against another klsh.h");
+  if (dst && dst->struct_size != sizeof(klsh_kmcdb_stats))
+    return set_error(KLSH_E_ARG, "klsh_kmcdb_stats.struct_size != sizeof: built against another klsh.h");
   klsh_kcount_stats local{};
   local.struct_size = sizeof(local);
+  klsh_kmcdb_stats dlocal{};
+  dlocal.struct_size = sizeof(dlocal);
   klsh::KcountHooks& hooks = klsh::ctx_kcount(ctx);  // test hooks; what this call reaches
   klsh::KmcHooks& bhooks = klsh::ctx_kmc(ctx);
   hooks.batches = hooks.rehashes = hooks.peak_slots = 0;
+  hooks.db_chunks = 0;
+  hooks.db_prefix_used = -1;
   hooks.values.clear();
   hooks.counts.clear();
   bhooks.decode_launches = 0;
@@ -361,6 +555,27 @@ extern "C" int klsh_count_khtable(klsh_ctx* ctx, const char* const* fastq_paths,
                                                   : "null FASTQ path");
     fclose(f);
   }
+  if (db_names) {  // and so does a database that could not be written
+    if (hooks.db_prefix >= 0 && !db_prefix_ok(k, hooks.db_prefix))
+      return set_error(KLSH_E_ARG, "kcount_db_prefix: not a prefix length of this k (p <= min(k, 15), "
+                                   "(k - p) % 4 == 0)");
+    for (int j = 0; j < n_samples; ++j) {
+      if (!db_names[j]) return set_error(KLSH_E_ARG, "null database name");
+      for (int i = 0; i < j; ++i)
+        if (!strcmp(db_names[i], db_names[j]))
+          return set_error(KLSH_E_ARG, (std::string("database named twice: ") + db_names[j]).c_str());
+    }
+    for (int j = 0; j < n_samples; ++j)
+      for (const char* ext : {".kmc_pre", ".kmc_suf"}) {
+        const std::string path = std::string(db_names[j]) + ext;
+        FILE* old = fopen(path.c_str(), "rb");  // a file the probe creates does not stay
+        if (old) fclose(old);
+        FILE* f = fopen(path.c_str(), "ab");
+        if (!f) return set_error(KLSH_E_ARG, ("cannot write " + path).c_str());
+        fclose(f);
+        if (!old) (void)remove(path.c_str());
+      }
+  }
   if (hipSetDevice(klsh::ctx_device(ctx)) != hipSuccess) return set_error(KLSH_E_HIP, "hipSetDevice");
   int rc;
   {
@@ -371,14 +586,25 @@ extern "C" int klsh_count_khtable(klsh_ctx* ctx, const char* const* fastq_paths,
       hooks.counts.resize(n_samples);
     }
     {
-      Counter counter(ctx, k, (uint32_t)(count_min < 1 ? 1 : count_min), local);
+      const uint32_t cmin = (uint32_t)(count_min < 1 ? 1 : count_min);
+      Counter counter(ctx, k, cmin, local);
+      DbWriter writer(ctx, k, cmin, dlocal);
       rc = counter.init();
-      for (int j = 0; j < n_samples && rc == KLSH_OK; ++j)
-        rc = counter.sample(fastq_paths[j], &src.ls[j],
-                            hooks.keep_listing ? &hooks.values[j] : nullptr,
+      if (rc == KLSH_OK && db_names) rc = writer.init();
+      for (int j = 0; j < n_samples && rc == KLSH_OK; ++j) {
+        Listing& l = src.ls[j];
+        rc = counter.sample(fastq_paths[j], &l, hooks.keep_listing ? &hooks.values[j] : nullptr,
                             hooks.keep_listing ? &hooks.counts[j] : nullptr);
+        if (rc == KLSH_OK && db_names) rc = writer.write(db_names[j], counter.values(), l.cnt, l.n);
+        if (!table) {  // nothing reads the listing again
+          if (l.rep) (void)hipFree(l.rep);
+          if (l.cnt) (void)hipFree(l.cnt);
+          l.rep = nullptr;
+          l.cnt = nullptr;
+        }
+      }
     }  // the sample table is freed before the union's
-    if (rc == KLSH_OK) {
+    if (rc == KLSH_OK && table) {
       klsh_khtable_stats bst{};
       bst.struct_size = sizeof(bst);
       rc = klsh::khtable_run(ctx, src, n_samples, k, out_dir, &bst);
@@ -392,5 +618,22 @@ extern "C" int klsh_count_khtable(klsh_ctx* ctx, const char* const* fastq_paths,
   }
   local.total_ms = now_ms() - t_start;
   if (st) *st = local;
+  if (dst) *dst = dlocal;
   return rc;
+}
+
+}  // namespace
+
+extern "C" int klsh_count_khtable(klsh_ctx* ctx, const char* const* fastq_paths, int n_samples,
+                                  int k, int count_min, const char* out_dir,
+                                  klsh_kcount_stats* st) {
+  return count_run(ctx, fastq_paths, nullptr, n_samples, k, count_min, out_dir, true, st, nullptr);
+}
+
+extern "C" int klsh_count_kmc(klsh_ctx* ctx, const char* const* fastq_paths,
+                              const char* const* db_names, int n_samples, int k, int count_min,
+                              const char* out_dir, klsh_kcount_stats* st, klsh_kmcdb_stats* dst) {
+  if (!db_names && !out_dir) return set_error(KLSH_E_ARG, "neither databases nor a table asked for");
+  return count_run(ctx, fastq_paths, db_names, n_samples, k, count_min, out_dir, out_dir != nullptr,
+                   st, dst);
 }

@@ -15,6 +15,8 @@
 //   k_kcount_collect  slots with count >= count_min -> (low word of the value, slot)
 //   k_kcount_hi       the values' high words, for the second sort pass (k > 16)
 //   k_kcount_emit     the listing in sorted order: value, rep image, min(count, 65535)
+//   k_kmcdb_pack      a chunk of the listing as the records of a KMC1-layout .kmc_suf
+//   k_kmcdb_lut       the .kmc_pre prefix table: per prefix, the records below it (binary search)
 //
 // The count word never wraps: a lane adds only while the count it sees is below 65535, so a slot
 // ends at most one in-flight add per wave above that (each at most 64), and every slot below
@@ -191,6 +193,60 @@ __global__ __launch_bounds__(256) void k_kcount_emit(const uint64_t* __restrict_
   }
 }
 
+// Records [r0, r0 + m) of a listing as the record bytes of a KMC1-layout .kmc_suf chunk: `suf`
+// suffix bytes (the low 8 suf bits of the value, most significant byte first), then the counter
+// in 2 bytes, little-endian.  A workgroup takes tiles of 256 records: each lane builds its record
+// in the LDS byte tile at lane * rec, and the tile (256 rec bytes, a multiple of 4; `out` is
+// 4-byte aligned) leaves as coalesced dword stores, the chunk's last partial tile's odd bytes as
+// byte stores.  Both loads are issued, on a clamped index, before the first LDS write.
+__global__ __launch_bounds__(256) void k_kmcdb_pack(const uint64_t* __restrict__ val,
+                                                    const uint32_t* __restrict__ cnt, uint64_t r0,
+                                                    uint64_t m, uint32_t suf,
+                                                    uint8_t* __restrict__ out) {
+  __shared__ uint32_t tile[256 * kKmcdbMaxRec / 4];
+  uint8_t* tb = reinterpret_cast<uint8_t*>(tile);
+  const uint32_t rec = suf + 2u, lane = threadIdx.x;
+  for (uint64_t base = blockIdx.x * 256ull; base < m; base += (uint64_t)gridDim.x * 256ull) {
+    const uint32_t nrec = (uint32_t)(m - base < 256u ? m - base : 256u);
+    const uint64_t i = r0 + base + (lane < nrec ? lane : nrec - 1u);  // in range for every lane
+    const uint64_t v = val[i];
+    const uint32_t c = cnt[i];
+    __syncthreads();  // the previous tile has been read out
+    uint8_t* q = tb + lane * rec;
+    for (uint32_t b = 0; b < suf; ++b) q[b] = (uint8_t)(v >> (8u * (suf - 1u - b)));
+    q[suf] = (uint8_t)c;
+    q[suf + 1u] = (uint8_t)(c >> 8);
+    __syncthreads();
+    const uint32_t nbytes = nrec * rec, nd = nbytes >> 2;
+    uint8_t* o = out + base * rec;
+    uint32_t* od = reinterpret_cast<uint32_t*>(o);
+    for (uint32_t d = lane; d < nd; d += 256u) od[d] = tile[d];
+    for (uint32_t b = (nd << 2) + lane; b < nbytes; b += 256u) o[b] = tb[b];
+  }
+}
+
+// lut[i] = the number of listed values below prefix q0 + i, i.e. the lower bound of
+// (q0 + i) << shift in val[0, n) (ascending); shift = 2 (k - p), 64 when k = 32 and p = 0 (the one
+// prefix 0, whose bound is 0).  An empty listing gives zeros.
+__global__ __launch_bounds__(256) void k_kmcdb_lut(const uint64_t* __restrict__ val, uint64_t n,
+                                                   uint64_t q0, uint64_t mq, uint32_t shift,
+                                                   uint64_t* __restrict__ lut) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < mq; i += (uint64_t)gridDim.x * 256ull) {
+    const uint64_t key = shift >= 64u ? 0ull : (q0 + i) << shift;
+    uint64_t lo = 0, len = n;
+    while (len) {
+      const uint64_t half = len >> 1;
+      if (val[lo + half] < key) {
+        lo += half + 1u;
+        len -= half + 1u;
+      } else {
+        len = half;
+      }
+    }
+    lut[i] = lo;
+  }
+}
+
 static uint32_t kc_grid(uint64_t n) {
   const uint64_t g = (n + 255) / 256;
   return (uint32_t)(g < 16384 ? (g ? g : 1) : 16384);
@@ -223,6 +279,14 @@ void launch_kcount_hi(const uint64_t* keys, const uint32_t* slots, uint64_t n, u
 void launch_kcount_emit(const uint64_t* keys, const uint32_t* cnt, const uint32_t* order, uint64_t n,
                         int k, uint64_t* val, uint64_t* rep, uint32_t* out_cnt, hipStream_t s) {
   if (n) k_kcount_emit<<<kc_grid(n), 256, 0, s>>>(keys, cnt, order, n, k, val, rep, out_cnt);
+}
+void launch_kmcdb_pack(const uint64_t* val, const uint32_t* cnt, uint64_t r0, uint64_t m,
+                       uint32_t sufix_size, uint8_t* out, hipStream_t s) {
+  if (m) k_kmcdb_pack<<<kc_grid(m), 256, 0, s>>>(val, cnt, r0, m, sufix_size, out);
+}
+void launch_kmcdb_lut(const uint64_t* val, uint64_t n, uint64_t q0, uint64_t mq, int k, int p,
+                      uint64_t* lut, hipStream_t s) {
+  if (mq) k_kmcdb_lut<<<kc_grid(mq), 256, 0, s>>>(val, n, q0, mq, (uint32_t)(2 * (k - p)), lut);
 }
 
 }  // namespace klsh

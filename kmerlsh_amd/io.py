@@ -10,6 +10,17 @@ from __future__ import annotations
 import numpy as np
 
 
+def kmc_prefix_length(k: int, n: int) -> int:
+    """The LUT prefix length p of the KMC database that mode K writes for a sample of n listed
+    k-mers (Engine.count_kmc, kmerLSH --kmc-db): among p in [0, min(k, 15)] with
+    (k - p) % 4 == 0, the one with the fewest bytes in .kmc_pre + .kmc_suf,
+    8 * 4^p + n * ((k - p) / 4 + 2); the smaller p on a tie."""
+    if not 1 <= k <= 32 or n < 0:
+        raise ValueError("k must be in [1, 32] and n >= 0")
+    return min(range(k % 4, min(k, 15) + 1, 4),
+               key=lambda p: (8 * 4 ** p + n * ((k - p) // 4 + 2), p))
+
+
 def count_lines(path: str) -> int:
     """Lines as std::getline counts them (io/ioHT.cc:3-19 GetInput)."""
     with open(path, "rb") as f:

@@ -3,6 +3,7 @@ GPU (synthetic data).
 
   python tools/bench_modes.py [--reads 2000000] [--kset 4000000] [--samples 8] [--kmers 4000000]
                               [--kreads 1000000] [--kgenome 4000000] [--only K|B|E]
+                              [--krepeat 1] [--kquick]
 
 Mode E: a FASTQ of random 150-bp reads, a third of them drawn from the sequence the k-mer set
 was cut from, through klsh_extract_fastq (host parse + GPU vote + writer); reports reads/s, k-mer
@@ -12,8 +13,12 @@ klsh_build_khtable; reports records/s.
 Mode K: two samples of `kreads` 150-bp reads each, either strand of a `kgenome`-base genome pool
 with 1 % substitutions, through klsh_count_khtable (host parse + GPU count + table build);
 reports k-mer positions/s, the counting kernels' time against the host parse time, rehashes and
-the peak table size — once from plain FASTQ, once with a quarter of the reads gzipped, and once
-on the worst case for same-address atomics, poly-A reads.  Prints one JSON line per run.
+the peak table size — once from plain FASTQ, once from the same files while also writing each
+sample's KMC database (klsh_count_kmc: the packing kernels' time, the host write time and the
+bytes written beside the same columns), once with a quarter of the reads gzipped, and once on the
+worst case for same-address atomics, poly-A reads.  --krepeat R repeats the plain run and the
+database run R times, alternating; --kquick leaves out the gzip and poly-A runs.  Prints one JSON
+line per run.
 """
 from __future__ import annotations
 
@@ -133,13 +138,30 @@ def _write_reads(path: str, seq: np.ndarray, gz: bool = False) -> None:
             f.write(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, seq[i].tobytes(), qual) for i in range(a, b)))
 
 
-def _count_run(engine, label: str, paths, k: int, count_min: int, tmp: str) -> dict:
-    engine.count_khtable(paths[:1], k, count_min, tmp)  # warm-up (page cache, code)
+def _count_run(engine, label: str, paths, k: int, count_min: int, tmp: str, db: bool = False,
+               warm: bool = True) -> dict:
+    names = [os.path.join(tmp, "db%d" % j) for j in range(len(paths))]
+    if warm:  # page cache, code
+        if db:
+            engine.count_kmc(paths[:1], names[:1], k, count_min, tmp)
+        else:
+            engine.count_khtable(paths[:1], k, count_min, tmp)
+    dst = {}
     t = time.perf_counter()
-    st = engine.count_khtable(paths, k, count_min, tmp)
+    if db:
+        st, dst = engine.count_kmc(paths, names, k, count_min, tmp)
+    else:
+        st = engine.count_khtable(paths, k, count_min, tmp)
     wall = time.perf_counter() - t
     kms = st["kernel_ms"]
-    return {"mode": "K", "input": label,
+    extra = {}
+    if db:
+        extra = {"wall_ms": wall * 1e3, "db_pack_ms": dst["pack_ms"], "db_write_ms": dst["write_ms"],
+                 "db_bytes": dst["bytes"], "db_records": dst["records"], "db_chunks": dst["chunks"],
+                 "db_prefix_len": [dst["prefix_len_min"], dst["prefix_len_max"]]}
+    else:
+        extra = {"wall_ms": wall * 1e3}
+    return {"mode": "K", "input": label, **extra,
             "metric": "k-mer positions/s (FASTQ parse + GPU count + table build)",
             "value": st["positions"] / wall, "k": k, "count_min": count_min, "samples": len(paths),
             "reads": st["reads"], "positions": st["positions"], "distinct": st["distinct"],
@@ -151,7 +173,8 @@ def _count_run(engine, label: str, paths, k: int, count_min: int, tmp: str) -> d
             "kernel_share_of_total": kms / st["total_ms"] if st["total_ms"] else None}
 
 
-def bench_count(engine, n_reads: int, n_genome: int, k: int = 31, count_min: int = 2) -> list:
+def bench_count(engine, n_reads: int, n_genome: int, k: int = 31, count_min: int = 2,
+                repeat: int = 1, quick: bool = False) -> list:
     rng = np.random.default_rng(7)
     pool = rng.integers(0, 4, size=n_genome, dtype=np.uint8)
     L = 150
@@ -172,7 +195,14 @@ def bench_count(engine, n_reads: int, n_genome: int, k: int = 31, count_min: int
             gz = os.path.join(tmp, "q%d.fq.gz" % j)
             _write_reads(gz, seq[:n_reads // 4], gz=True)
             mixed.append(gz)
-        out.append(_count_run(engine, "plain FASTQ", plain, k, count_min, tmp))
+        has_db = hasattr(engine._lib, "klsh_count_kmc")  # an A/B build of an older engine has none
+        for r in range(repeat):
+            out.append(_count_run(engine, "plain FASTQ", plain, k, count_min, tmp, warm=r == 0))
+            if has_db:
+                out.append(_count_run(engine, "plain FASTQ, KMC databases written", plain, k,
+                                      count_min, tmp, db=True, warm=r == 0))
+        if quick:
+            return out
         out.append(_count_run(engine, "gzip FASTQ (a quarter of the reads)", mixed, k, count_min, tmp))
         # worst case for same-address atomics: every window of every read is the same k-mer
         poly = os.path.join(tmp, "polyA.fq")
@@ -190,6 +220,8 @@ def main() -> None:
     ap.add_argument("--kreads", type=int, default=1000000)
     ap.add_argument("--kgenome", type=int, default=4000000)
     ap.add_argument("--only", choices=("K", "B", "E"), default=None)
+    ap.add_argument("--krepeat", type=int, default=1)
+    ap.add_argument("--kquick", action="store_true")
     a = ap.parse_args()
     from kmerlsh_amd import _native
 
@@ -199,7 +231,7 @@ def main() -> None:
         if a.only in (None, "B"):
             print(json.dumps(bench_khtable(eng, a.samples, a.kmers)), flush=True)
         if a.only in (None, "K"):
-            for row in bench_count(eng, a.kreads, a.kgenome):
+            for row in bench_count(eng, a.kreads, a.kgenome, repeat=a.krepeat, quick=a.kquick):
                 print(json.dumps(row), flush=True)
 
 
