@@ -157,7 +157,9 @@ int klsh_comm_init(klsh_ctx* ctx, int rank, int world, const uint8_t* id /* 128 
  * klsh_cluster must then run on its own host thread, concurrently.  For tests on one GPU. */
 int klsh_comm_init_local(klsh_ctx** ctxs, int world);
 int klsh_comm_info(klsh_ctx* ctx, int* rank, int* world);
-/* Options of a context.  Results never depend on them, except "stop_after".
+/* Options of a context.  Results never depend on them, except "stop_after"
+ * (tests/test_gpu_launch_geometry.py holds that claim for the launch sizes: every one of them at
+ * 1, and "grid_cap" at 1 to 3, against the oracle and the models).
  *   "shard_min_rows"   sharded loop: below this many live rows every rank runs the remaining
  *                      iterations on its own replica, without exchanges (default 2^21; 0 = always)
  *   "phase_timing"     0/1: per-phase HIP events (adds latency; default 0)
@@ -176,9 +178,20 @@ int klsh_comm_info(klsh_ctx* ctx, int* rank, int* world);
  *                      reaches them (0 = default: all of them while they fit in 256 MB, else 64
  *                      iterations' worth)
  *   "comm_timeout_s"   a collective still incomplete after this many seconds aborts (default 600)
- *   launch sizes, 0 = the measured default: "h16_grid", "wide_grid", "fix_grid" (projection),
- *   "small_grid", "tail_big_groups", "tail_small_groups", "wide_group_grid",
- *   "small_screen_grid" (merge);
+ *   launch sizes, 0 = the measured default, from 1 workgroup on: "h16_grid", "wide_grid",
+ *   "fix_grid" (projection), "small_grid", "tail_big_groups", "tail_small_groups",
+ *   "wide_group_grid", "small_screen_grid" (merge);
+ *   "grid_cap"         (tests) N in [1, 2^20]: at most N workgroups for every launch that strides
+ *                      over a list or an index range and has no size option of its own — the
+ *                      per-class merges of 65-row and longer runs (k_merge_big, k_merge_big_wide,
+ *                      k_merge_huge, k_merge_long, whose bit matrices stay allocated for the
+ *                      uncapped count), the kernels of modes K, B and E, and the sharded loop's
+ *                      bin histogram and delta pack / apply; 0 (default) = off.  It does not
+ *                      reach the launches with one workgroup per tile, nor the kernels whose
+ *                      workgroups wait for one another (the look-back scans and compaction, the
+ *                      sort passes, the run listing, the local tail sort, the partition, the
+ *                      packed and generic projections): fewer workgroups than tiles there is a
+ *                      wrong result or a spin that runs into its limit
  *   "small_screen"     1 = runs of 2..64 rows are screened on the fp16 row image first and only
  *                      the ones the screen cannot rule out are merged on the f32 rows
  *   "tail_screen"      1 (default) = the fp16 small-run screen also runs in front of the one-launch

@@ -769,6 +769,7 @@ int ctx_device(const klsh_ctx* ctx) { return ctx->device; }
 hipStream_t ctx_stream(const klsh_ctx* ctx) { return ctx->stream; }
 KmcHooks& ctx_kmc(klsh_ctx* ctx) { return ctx->kmc; }
 KcountHooks& ctx_kcount(klsh_ctx* ctx) { return ctx->kcount; }
+uint32_t ctx_grid_cap(const klsh_ctx* ctx) { return ctx->mw.grid_cap; }
 int set_error(int code, const char* msg) { return fail(code, msg); }
 }  // namespace klsh
 
@@ -1616,7 +1617,7 @@ static int cluster_sharded_body(klsh_ctx* ctx, float min_similarity, int iterati
     const int B = std::min(h, klsh::kMaxBinBits);
     const int shift = h - B;
     const uint32_t nbins = 1u << B;
-    klsh::launch_bin_hist(ctx->keys, n_g, shift, nbins, ctx->bins, s);
+    klsh::launch_bin_hist(ctx->keys, n_g, shift, nbins, ctx->bins, s, ctx->mw.grid_cap);
     if (timed_comm([&] { return cm->allgather(ctx->bins, ctx->bins_all, 4ull * nbins, s); }))
       return comm_fail("bin histogram allgather");
     klsh::launch_bin_split(ctx->bins_all, W, nbins, N, ctx->owner, ctx->cntmat, s);
@@ -1741,12 +1742,12 @@ static int cluster_sharded_body(klsh_ctx* ctx, float min_similarity, int iterati
     if (nd_all) {
       if (int e = ctx->reserve_words(&ctx->drec, &ctx->drec_cap, (size_t)R * ndel[g] + 1)) return e;
       if (int e = ctx->reserve_words(&ctx->drec_all, &ctx->drec_all_cap, (size_t)R * nd_all)) return e;
-      klsh::launch_delta_pack(ctx->rows, ctx->dslots, ndel[g], ctx->drec, s);
+      klsh::launch_delta_pack(ctx->rows, ctx->dslots, ndel[g], ctx->drec, s, ctx->mw.grid_cap);
       if (timed_comm([&] {
             return cm->allgatherv(ctx->drec, ctx->drec_all, dcnt.data(), doff.data(), s);
           }))
         return comm_fail("delta allgather");
-      klsh::launch_delta_apply(ctx->rows, ctx->drec_all, (uint32_t)nd_all, s);
+      klsh::launch_delta_apply(ctx->rows, ctx->drec_all, (uint32_t)nd_all, s, ctx->mw.grid_cap);
       KLSH_HIP(hipGetLastError());
     }
 
@@ -2042,6 +2043,11 @@ int klsh_set_option(klsh_ctx* ctx, const char* name, int64_t value) {
   if (n == "tail_small_groups") return grid(&ctx->mw.tail_nsmall);
   if (n == "wide_group_grid") return grid(&ctx->mw.wide_group_grid);
   if (n == "small_screen_grid") return grid(&ctx->mw.screen_grid);
+  if (n == "grid_cap") {  // one option, kept where each mode's launches read it
+    if (int e = grid(&ctx->mw.grid_cap)) return e;
+    ctx->kmc.grid_cap = ctx->kcount.grid_cap = ctx->mw.grid_cap;
+    return 0;
+  }
   if (n == "tail_merge_rows") {
     // capped at the largest size the one-launch merge's parity is pinned at (2^22: C2's
     // iterations of 2^21..2^22 positions, test_mid_local_sort's 2.6M rows); above it, runs over
@@ -2114,6 +2120,7 @@ int klsh_get_option(klsh_ctx* ctx, const char* name, int64_t* value) {
   else if (n == "tail_small_groups") *value = ctx->mw.tail_nsmall;
   else if (n == "wide_group_grid") *value = ctx->mw.wide_group_grid;
   else if (n == "small_screen_grid") *value = ctx->mw.screen_grid;
+  else if (n == "grid_cap") *value = ctx->mw.grid_cap;
   else if (n == "tail_merge_rows") *value = klsh::tail_merge_max(ctx->mw);
   else if (n == "small_screen") *value = ctx->mw.small_screen;
   else if (n == "hip_events") *value = ctx->hip_events ? 1 : 0;

@@ -624,7 +624,7 @@ klsh_kset* klsh_kset_create(klsh_ctx* ctx, const uint64_t* kmers, uint64_t n, in
   ok = ok && hipMemsetAsync(ks->tab, 0xFF, cap * 8, s) == hipSuccess;
   ok = ok && (n == 0 || hipMemcpyAsync(dk, kmers, n * 8, hipMemcpyHostToDevice, s) == hipSuccess);
   if (ok) {
-    klsh::launch_kset_insert(dk, n, ks->tab, ks->mask, s);
+    klsh::launch_kset_insert(dk, n, ks->tab, ks->mask, s, klsh::ctx_grid_cap(ctx));
     ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
   }
   if (dk) (void)hipFree(dk);
@@ -666,7 +666,8 @@ int klsh_check_reads(klsh_ctx* ctx, const klsh_kset* ks, const char* seq,
   ok = ok && hipMemcpyAsync(dseq, seq + read_offsets[0], nb, hipMemcpyHostToDevice, s) == hipSuccess &&
        hipMemcpyAsync(doff, off.data(), off.size() * 8, hipMemcpyHostToDevice, s) == hipSuccess;
   if (ok) {
-    klsh::launch_check_reads(dseq, doff, n_reads, k, kmer_vote, ks->tab, ks->mask, dhit, dflag, s);
+    klsh::launch_check_reads(dseq, doff, n_reads, k, kmer_vote, ks->tab, ks->mask, dhit, dflag, s,
+                             klsh::ctx_grid_cap(ctx));
     ok = hipGetLastError() == hipSuccess;
   }
   ok = ok && (!hits || hipMemcpyAsync(hits, dhit, n_reads * 4, hipMemcpyDeviceToHost, s) == hipSuccess) &&
@@ -755,7 +756,7 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
     KLSH_XHIP(hipMemcpyAsync(sl.doff, b.seq_off.data(), (sl.n + 1) * 8, hipMemcpyHostToDevice, s));
     KLSH_XHIP(hipEventRecord(sl.e0, s));
     klsh::launch_check_reads(sl.dseq, sl.doff, sl.n, k, kmer_vote, ks->tab, ks->mask, sl.dhit,
-                             sl.dflag, s);
+                             sl.dflag, s, klsh::ctx_grid_cap(ctx));
     KLSH_XHIP(hipGetLastError());
     KLSH_XHIP(hipEventRecord(sl.e1, s));
     KLSH_XHIP(hipMemcpyAsync(sl.hflag, sl.dflag, sl.n, hipMemcpyDeviceToHost, s));

@@ -130,20 +130,20 @@ __global__ __launch_bounds__(256) void k_check_reads(const uint8_t* __restrict__
 }
 
 void launch_kset_insert(const uint64_t* kmers, uint64_t n, uint64_t* tab, uint64_t mask,
-                        hipStream_t s) {
+                        hipStream_t s, uint32_t grid_cap) {
   if (n == 0) return;
   const uint64_t g = (n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192;
-  k_kset_insert<<<(uint32_t)g, 256, 0, s>>>(kmers, n, reinterpret_cast<unsigned long long*>(tab),
-                                            mask);
+  k_kset_insert<<<cap_grid((uint32_t)g, grid_cap), 256, 0, s>>>(
+      kmers, n, reinterpret_cast<unsigned long long*>(tab), mask);
 }
 
 void launch_check_reads(const uint8_t* seq, const uint64_t* off, uint64_t n, int k, float vote,
                         const uint64_t* tab, uint64_t mask, uint32_t* hits, uint8_t* flags,
-                        hipStream_t s) {
+                        hipStream_t s, uint32_t grid_cap) {
   if (n == 0) return;
   const uint64_t w = (n + kCheckWaves - 1) / kCheckWaves, g = w < 16384 ? w : 16384;
-  k_check_reads<<<(uint32_t)g, 64 * kCheckWaves, 0, s>>>(seq, off, n, k, vote, tab, mask, hits,
-                                                         flags);
+  k_check_reads<<<cap_grid((uint32_t)g, grid_cap), 64 * kCheckWaves, 0, s>>>(
+      seq, off, n, k, vote, tab, mask, hits, flags);
 }
 
 }  // namespace klsh

@@ -184,6 +184,9 @@ struct MergeWork {
   // "tail_merge_rows": below this many positions every merge class runs in ONE launch
   // (k_merge_tail); 0 = the default 2^22 (tests lower it to reach the per-class launches)
   uint32_t tail_max;
+  // "grid_cap" (tests): at most this many workgroups for the per-class launches that stride over
+  // a run list (k_merge_big, k_merge_big_wide, k_merge_huge, k_merge_long); 0 = off
+  uint32_t grid_cap = 0;
   hipStream_t aux[3];
   KTime kt;                // per-class stamps of this iteration's merge launches
   hipEvent_t small_ev[2];  // HIP events around the small-run launch (nullptr: not recorded)
@@ -191,6 +194,10 @@ struct MergeWork {
   hipEvent_t join[3];
 };
 constexpr int kMergeStreams = 3;
+// Option "grid_cap" (tests; 0 = off): g workgroups, at most `cap`.  Only for launches whose
+// workgroups stride over a list or an index range on their own; a kernel whose workgroups take
+// one tile each, or wait for one another, must keep its grid.
+inline uint32_t cap_grid(uint32_t g, uint32_t cap) { return cap && g > cap ? cap : g; }
 constexpr uint32_t kLongRows = 4096;  // the longest run k_merge_long walks (longer: k_merge_huge)
 inline bool long_ok(int d) { return d == 16 || d == 32; }
 // (2^22 since round 5: with the small-run screen and the big-run prescreen inside it, the one
@@ -394,8 +401,9 @@ constexpr int kMaxBinBits = 12;           // key ranges are unions of 2^12 top-b
 constexpr int kMaxRanks = 64;
 
 // hist[bin] += 1 for every key (bin = key >> shift, < nbins); hist zeroed by the caller.
+// grid_cap (here and below): option "grid_cap", 0 = off (cap_grid).
 void launch_bin_hist(const uint32_t* keys, uint32_t n, int shift, uint32_t nbins, uint32_t* hist,
-                     hipStream_t s);
+                     hipStream_t s, uint32_t grid_cap = 0);
 // From every rank's histogram (hist_all[W][nbins]) and the total row count: owner[bin] = the rank
 // owning the bin (contiguous, balanced by rows), cntmat[g * W + r] = rows rank g sends rank r.
 void launch_bin_split(const uint32_t* hist_all, int world, uint32_t nbins, uint64_t total,
@@ -418,8 +426,9 @@ void launch_unpack_pairs(const uint2* in, uint32_t n, uint32_t* keys, uint32_t* 
 // Delta records, stride 5 + dp words: slot, cnt, head, tail, nrm bits, row[dp].
 __host__ __device__ inline int delta_words(int dp) { return 5 + dp; }
 void launch_delta_pack(const Rows& r, const uint32_t* delta_slots, uint32_t n, uint32_t* rec,
-                       hipStream_t s);
-void launch_delta_apply(const Rows& r, const uint32_t* rec, uint32_t n, hipStream_t s);
+                       hipStream_t s, uint32_t grid_cap = 0);
+void launch_delta_apply(const Rows& r, const uint32_t* rec, uint32_t n, hipStream_t s,
+                        uint32_t grid_cap = 0);
 // Merge profile of the diagnostics build (-DKLSH_MERGE_PROF): print and clear.
 void merge_prof_dump(FILE* f);
 
@@ -429,12 +438,12 @@ void launch_min_u32(uint32_t* a, const uint32_t* b, size_t n, hipStream_t s);
 // ---- mode E (klsh_extract.hip): differential k-mer sets and the per-read k-mer vote ----------
 // tab: `mask + 1` (a power of two) 64-bit slots, all ones = empty; kmers[i] == all ones skipped.
 void launch_kset_insert(const uint64_t* kmers, uint64_t n, uint64_t* tab, uint64_t mask,
-                        hipStream_t s);
+                        hipStream_t s, uint32_t grid_cap = 0);
 // Read r = seq[off[r] .. off[r+1]): hits[r] = its k-mer positions whose canonical k-mer is in the
 // set, flags[r] = hits / (len - k + 1) > vote (float), both 0 for reads shorter than k + 10.
 void launch_check_reads(const uint8_t* seq, const uint64_t* off, uint64_t n, int k, float vote,
                         const uint64_t* tab, uint64_t mask, uint32_t* hits, uint8_t* flags,
-                        hipStream_t s);
+                        hipStream_t s, uint32_t grid_cap = 0);
 
 // ---- mode B (klsh_kmc.hip): the k-mer table of KMC databases ---------------------------------
 struct KmcParams {
@@ -451,20 +460,20 @@ struct KmcParams {
 // total + 1 sentinel.
 void launch_kmc_decode(const uint8_t* recs, uint64_t n, uint64_t rec0, const KmcParams& kp,
                        const uint64_t* lut, uint64_t lut_n, uint64_t* rep, uint32_t* cnt,
-                       uint32_t* n_valid, hipStream_t s);
+                       uint32_t* n_valid, hipStream_t s, uint32_t grid_cap = 0);
 void launch_kmc_union(const uint64_t* rep, uint64_t n, uint64_t ord0, uint64_t* tab,
-                      uint64_t* first, uint64_t mask, hipStream_t s);
+                      uint64_t* first, uint64_t mask, hipStream_t s, uint32_t grid_cap = 0);
 void launch_kmc_count(const uint64_t* rep, const uint32_t* cnt, uint64_t n, const uint64_t* tab,
-                      uint64_t mask, uint32_t* acc, hipStream_t s);
+                      uint64_t mask, uint32_t* acc, hipStream_t s, uint32_t grid_cap = 0);
 // occupied slots -> (low word of their first-appearance ordinal, slot), *n_out of them
 void launch_kmc_collect(const uint64_t* tab, const uint64_t* first, uint64_t cap, uint32_t* lo,
-                        uint32_t* slot, uint32_t* n_out, hipStream_t s);
+                        uint32_t* slot, uint32_t* n_out, hipStream_t s, uint32_t grid_cap = 0);
 void launch_kmc_hi(const uint64_t* first, const uint32_t* slots, uint64_t n, uint32_t* hi,
-                   hipStream_t s);
+                   hipStream_t s, uint32_t grid_cap = 0);
 void launch_kmc_emit_keys(const uint64_t* tab, const uint32_t* order, uint64_t n, uint64_t* out,
-                          hipStream_t s);
+                          hipStream_t s, uint32_t grid_cap = 0);
 void launch_kmc_emit(const uint32_t* acc, const uint32_t* order, uint64_t n, uint16_t* out,
-                     hipStream_t s);
+                     hipStream_t s, uint32_t grid_cap = 0);
 
 // klsh_build_khtable's test hooks and what its last call on the context reached (options
 // "kmc_chunk_records", "kmc_ordinal_base", "kmc_keep_first"; read-only "kmc_decode_launches",
@@ -475,6 +484,7 @@ struct KmcHooks {
   bool keep_first = false;       // keep the first-appearance list of the next calls in `first`
   uint64_t decode_launches = 0;  // pass 1's k_kmc_decode launches
   int high_sort = 0;             // 1 = the ordinals' high words were sorted
+  uint32_t grid_cap = 0;         // "grid_cap": workgroups per launch of the table build, at most
   std::vector<uint64_t> first;   // distinct canonical k-mers by first ordinal
 };
 
@@ -509,28 +519,30 @@ constexpr uint32_t kKcountWindow = 2048;  // k-mer positions per LDS window (per
 // reads seq[off[r] .. off[r+1]) counted into the table (keys: mask + 1 slots, all ones = empty;
 // cnt: their occurrence counts); ctr[0] += slots claimed, ctr[1] += valid k-mer windows
 void launch_kcount_reads(const uint8_t* seq, const uint64_t* off, uint64_t n, int k, uint64_t* keys,
-                         uint32_t* cnt, uint64_t mask, uint64_t* ctr, hipStream_t s);
+                         uint32_t* cnt, uint64_t mask, uint64_t* ctr, hipStream_t s,
+                         uint32_t grid_cap = 0);
 // every entry of the old table into the (empty) new one
 void launch_kcount_rehash(const uint64_t* okeys, const uint32_t* ocnt, uint64_t ocap, uint64_t* keys,
-                          uint32_t* cnt, uint64_t mask, hipStream_t s);
+                          uint32_t* cnt, uint64_t mask, hipStream_t s, uint32_t grid_cap = 0);
 // slots with count >= count_min -> (low word of their KMC value, slot), *n_out of them
 void launch_kcount_collect(const uint64_t* keys, const uint32_t* cnt, uint64_t cap,
                            uint32_t count_min, uint32_t* lo, uint32_t* slot, uint32_t* n_out,
-                           hipStream_t s);
+                           hipStream_t s, uint32_t grid_cap = 0);
 void launch_kcount_hi(const uint64_t* keys, const uint32_t* slots, uint64_t n, uint32_t* hi,
-                      hipStream_t s);
+                      hipStream_t s, uint32_t grid_cap = 0);
 // the listing in `order`: KMC value, canonical Kmer image, min(count, 65535)
 void launch_kcount_emit(const uint64_t* keys, const uint32_t* cnt, const uint32_t* order, uint64_t n,
-                        int k, uint64_t* val, uint64_t* rep, uint32_t* out_cnt, hipStream_t s);
+                        int k, uint64_t* val, uint64_t* rep, uint32_t* out_cnt, hipStream_t s,
+                        uint32_t grid_cap = 0);
 // A listing as a KMC1-layout database (klsh_count_kmc): records [r0, r0 + m) of (val, cnt) as
 // .kmc_suf record bytes in out[0, m * (sufix_size + 2)) — sufix_size = (k - p) / 4 big-endian
 // suffix bytes, then the 2-byte little-endian counter; out 4-byte aligned
 constexpr uint32_t kKmcdbMaxRec = 10;  // k = 32, p = 0: 8 suffix bytes + the counter
 void launch_kmcdb_pack(const uint64_t* val, const uint32_t* cnt, uint64_t r0, uint64_t m,
-                       uint32_t sufix_size, uint8_t* out, hipStream_t s);
+                       uint32_t sufix_size, uint8_t* out, hipStream_t s, uint32_t grid_cap = 0);
 // lut[i] = records whose prefix (val >> 2 (k - p)) is below q0 + i, for i < mq; val: n ascending
 void launch_kmcdb_lut(const uint64_t* val, uint64_t n, uint64_t q0, uint64_t mq, int k, int p,
-                      uint64_t* lut, hipStream_t s);
+                      uint64_t* lut, hipStream_t s, uint32_t grid_cap = 0);
 
 // klsh_count_khtable's / klsh_count_kmc's test hooks and what the last call on the context
 // reached (options "kcount_batch_reads", "kcount_table_slots", "kcount_keep_listing",
@@ -547,6 +559,7 @@ struct KcountHooks {
   uint64_t db_chunk_records = 0;   // records per .kmc_suf chunk (0 = 2^22)
   uint64_t db_chunks = 0;          // k_kmcdb_pack launches of the last call
   int db_prefix_used = -1;         // the prefix length of its last database (-1 = none written)
+  uint32_t grid_cap = 0;           // "grid_cap": workgroups per counting / packing launch, at most
   std::vector<std::vector<uint64_t>> values;  // per sample: the listed KMC values, ascending
   std::vector<std::vector<uint32_t>> counts;
 };
@@ -557,6 +570,7 @@ int ctx_device(const klsh_ctx* ctx);
 hipStream_t ctx_stream(const klsh_ctx* ctx);
 KmcHooks& ctx_kmc(klsh_ctx* ctx);
 KcountHooks& ctx_kcount(klsh_ctx* ctx);
+uint32_t ctx_grid_cap(const klsh_ctx* ctx);  // option "grid_cap" (mode E's launches)
 int set_error(int code, const char* msg);  // sets klsh_last_error(), returns code
 
 }  // namespace klsh

@@ -208,7 +208,8 @@ class DbWriter {
       Buf& b = buf_[(r0 / per) & 1];
       const uint64_t m = std::min<uint64_t>(per, n - r0);
       KLSH_CRET(hipEventRecord(b.e0, s_));
-      klsh::launch_kmcdb_pack(val, cnt, r0, m, sufix, dev_, s_);
+      klsh::launch_kmcdb_pack(val, cnt, r0, m, sufix, dev_, s_,
+                              hooks_.grid_cap);
       KLSH_CRET(hipGetLastError());
       KLSH_CRET(hipEventRecord(b.e1, s_));
       KLSH_CRET(hipMemcpyAsync(b.host, dev_, m * rec, hipMemcpyDeviceToHost, s_));
@@ -236,7 +237,8 @@ class DbWriter {
       Buf& b = buf_[(q0 / per) & 1];
       const uint64_t mq = std::min<uint64_t>(per, entries - q0);
       KLSH_CRET(hipEventRecord(b.e0, s_));
-      klsh::launch_kmcdb_lut(val, n, q0, mq, k_, p, reinterpret_cast<uint64_t*>(dev_), s_);
+      klsh::launch_kmcdb_lut(val, n, q0, mq, k_, p, reinterpret_cast<uint64_t*>(dev_), s_,
+                             hooks_.grid_cap);
       KLSH_CRET(hipGetLastError());
       KLSH_CRET(hipEventRecord(b.e1, s_));
       KLSH_CRET(hipMemcpyAsync(b.host, dev_, mq * 8, hipMemcpyDeviceToHost, s_));
@@ -340,7 +342,8 @@ class Counter {
       hipError_t e = hipMemsetAsync(nkeys, 0xFF, ncap * 8, s_);
       if (e == hipSuccess) e = hipMemsetAsync(ncnt, 0, ncap * 4, s_);
       if (e == hipSuccess) {
-        klsh::launch_kcount_rehash(keys_, cnt_, cap_, nkeys, ncnt, ncap - 1, s_);
+        klsh::launch_kcount_rehash(keys_, cnt_, cap_, nkeys, ncnt, ncap - 1, s_,
+                                   hooks_.grid_cap);
         e = hipGetLastError();
       }
       if (e == hipSuccess) e = hipStreamSynchronize(s_);
@@ -380,7 +383,8 @@ class Counter {
     if (nb) KLSH_CRET(hipMemcpyAsync(sl.dseq, sl.seq.data(), nb, hipMemcpyHostToDevice, s_));
     KLSH_CRET(hipMemcpyAsync(sl.doff, sl.off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s_));
     KLSH_CRET(hipEventRecord(sl.e0, s_));
-    klsh::launch_kcount_reads(sl.dseq, sl.doff, n, k_, keys_, cnt_, cap_ - 1, ctr_, s_);
+    klsh::launch_kcount_reads(sl.dseq, sl.doff, n, k_, keys_, cnt_, cap_ - 1, ctr_, s_,
+                              hooks_.grid_cap);
     KLSH_CRET(hipGetLastError());
     KLSH_CRET(hipEventRecord(sl.e1, s_));
     KLSH_CRET(hipMemcpyAsync(hctr_, ctr_, 16, hipMemcpyDeviceToHost, s_));
@@ -465,7 +469,8 @@ class Counter {
     uint32_t* nout = reinterpret_cast<uint32_t*>(ctr_ + 4);
     uint32_t n = 0;
     KLSH_CRET(hipMemsetAsync(nout, 0, 4, s_));
-    klsh::launch_kcount_collect(keys_, cnt_, cap_, count_min_, lo_, sl_, nout, s_);
+    klsh::launch_kcount_collect(keys_, cnt_, cap_, count_min_, lo_, sl_, nout, s_,
+                                hooks_.grid_cap);
     KLSH_CRET(hipGetLastError());
     KLSH_CRET(hipMemcpyAsync(&n, nout, 4, hipMemcpyDeviceToHost, s_));
     KLSH_CRET(hipStreamSynchronize(s_));
@@ -475,7 +480,8 @@ class Counter {
     if (n && k_ > 16) {
       uint32_t* hk = ok == lo_ ? lo2_ : lo_;  // the free key buffer
       uint32_t* hv = ov == sl_ ? sl2_ : sl_;
-      klsh::launch_kcount_hi(keys_, ov, n, hk, s_);
+      klsh::launch_kcount_hi(keys_, ov, n, hk, s_,
+                             hooks_.grid_cap);
       uint32_t *ok2 = nullptr, *ov2 = nullptr;
       klsh::radix_sort(hk, ov, ok, hv, n, 2 * k_ - 32, ws_, &ok2, &ov2, s_);
       ov = ov2;
@@ -484,7 +490,8 @@ class Counter {
     out->n = n;
     KLSH_CRET(hipMalloc((void**)&out->rep, (uint64_t)(n ? n : 1) * 8));
     KLSH_CRET(hipMalloc((void**)&out->cnt, (uint64_t)(n ? n : 1) * 4));
-    klsh::launch_kcount_emit(keys_, cnt_, ov, n, k_, val_, out->rep, out->cnt, s_);
+    klsh::launch_kcount_emit(keys_, cnt_, ov, n, k_, val_, out->rep, out->cnt, s_,
+                             hooks_.grid_cap);
     KLSH_CRET(hipGetLastError());
     std::vector<uint32_t> hcnt(n);
     if (n) KLSH_CRET(hipMemcpyAsync(hcnt.data(), out->cnt, n * 4ull, hipMemcpyDeviceToHost, s_));

@@ -247,46 +247,51 @@ __global__ __launch_bounds__(256) void k_kmcdb_lut(const uint64_t* __restrict__ 
   }
 }
 
-static uint32_t kc_grid(uint64_t n) {
+static uint32_t kc_grid(uint64_t n, uint32_t grid_cap) {
   const uint64_t g = (n + 255) / 256;
-  return (uint32_t)(g < 16384 ? (g ? g : 1) : 16384);
+  return cap_grid((uint32_t)(g < 16384 ? (g ? g : 1) : 16384), grid_cap);
 }
 
 void launch_kcount_reads(const uint8_t* seq, const uint64_t* off, uint64_t n, int k, uint64_t* keys,
-                         uint32_t* cnt, uint64_t mask, uint64_t* ctr, hipStream_t s) {
+                         uint32_t* cnt, uint64_t mask, uint64_t* ctr, hipStream_t s,
+                         uint32_t grid_cap) {
   if (n == 0) return;
   // at most 4096 workgroups: each wave ends with two adds to ctr
   const uint64_t w = (n + kKcWaves - 1) / kKcWaves, g = w < 4096 ? w : 4096;
-  k_kcount_reads<<<(uint32_t)g, 64 * kKcWaves, 0, s>>>(
+  k_kcount_reads<<<cap_grid((uint32_t)g, grid_cap), 64 * kKcWaves, 0, s>>>(
       seq, off, n, k, reinterpret_cast<unsigned long long*>(keys), cnt, mask,
       reinterpret_cast<unsigned long long*>(ctr));
 }
 void launch_kcount_rehash(const uint64_t* okeys, const uint32_t* ocnt, uint64_t ocap, uint64_t* keys,
-                          uint32_t* cnt, uint64_t mask, hipStream_t s) {
-  k_kcount_rehash<<<kc_grid(ocap), 256, 0, s>>>(okeys, ocnt, ocap,
-                                                reinterpret_cast<unsigned long long*>(keys), cnt,
-                                                mask);
+                          uint32_t* cnt, uint64_t mask, hipStream_t s, uint32_t grid_cap) {
+  k_kcount_rehash<<<kc_grid(ocap, grid_cap), 256, 0, s>>>(okeys, ocnt, ocap,
+                                                          reinterpret_cast<unsigned long long*>(keys),
+                                                          cnt, mask);
 }
 void launch_kcount_collect(const uint64_t* keys, const uint32_t* cnt, uint64_t cap,
                            uint32_t count_min, uint32_t* lo, uint32_t* slot, uint32_t* n_out,
-                           hipStream_t s) {
-  k_kcount_collect<<<kc_grid(cap), 256, 0, s>>>(keys, cnt, cap, count_min, lo, slot, n_out);
+                           hipStream_t s, uint32_t grid_cap) {
+  k_kcount_collect<<<kc_grid(cap, grid_cap), 256, 0, s>>>(keys, cnt, cap, count_min, lo, slot,
+                                                          n_out);
 }
 void launch_kcount_hi(const uint64_t* keys, const uint32_t* slots, uint64_t n, uint32_t* hi,
-                      hipStream_t s) {
-  if (n) k_kcount_hi<<<kc_grid(n), 256, 0, s>>>(keys, slots, n, hi);
+                      hipStream_t s, uint32_t grid_cap) {
+  if (n) k_kcount_hi<<<kc_grid(n, grid_cap), 256, 0, s>>>(keys, slots, n, hi);
 }
 void launch_kcount_emit(const uint64_t* keys, const uint32_t* cnt, const uint32_t* order, uint64_t n,
-                        int k, uint64_t* val, uint64_t* rep, uint32_t* out_cnt, hipStream_t s) {
-  if (n) k_kcount_emit<<<kc_grid(n), 256, 0, s>>>(keys, cnt, order, n, k, val, rep, out_cnt);
+                        int k, uint64_t* val, uint64_t* rep, uint32_t* out_cnt, hipStream_t s,
+                        uint32_t grid_cap) {
+  if (n)
+    k_kcount_emit<<<kc_grid(n, grid_cap), 256, 0, s>>>(keys, cnt, order, n, k, val, rep, out_cnt);
 }
 void launch_kmcdb_pack(const uint64_t* val, const uint32_t* cnt, uint64_t r0, uint64_t m,
-                       uint32_t sufix_size, uint8_t* out, hipStream_t s) {
-  if (m) k_kmcdb_pack<<<kc_grid(m), 256, 0, s>>>(val, cnt, r0, m, sufix_size, out);
+                       uint32_t sufix_size, uint8_t* out, hipStream_t s, uint32_t grid_cap) {
+  if (m) k_kmcdb_pack<<<kc_grid(m, grid_cap), 256, 0, s>>>(val, cnt, r0, m, sufix_size, out);
 }
 void launch_kmcdb_lut(const uint64_t* val, uint64_t n, uint64_t q0, uint64_t mq, int k, int p,
-                      uint64_t* lut, hipStream_t s) {
-  if (mq) k_kmcdb_lut<<<kc_grid(mq), 256, 0, s>>>(val, n, q0, mq, (uint32_t)(2 * (k - p)), lut);
+                      uint64_t* lut, hipStream_t s, uint32_t grid_cap) {
+  if (mq)
+    k_kmcdb_lut<<<kc_grid(mq, grid_cap), 256, 0, s>>>(val, n, q0, mq, (uint32_t)(2 * (k - p)), lut);
 }
 
 }  // namespace klsh

@@ -862,7 +862,7 @@ static void launch_h16(const Rows& r, const uint32_t* slots, uint32_t* keys, uin
                        const float* W, int h, uint32_t key_or, hipStream_t s,
                        const ProjectWork& pw, KTime kt, const uint32_t* n_dev,
                        const uint32_t* woff_dev) {
-  const uint32_t gmax = pw.h16_grid ? std::max(256u, pw.h16_grid) : kH16Grid;  // "h16_grid"
+  const uint32_t gmax = pw.h16_grid ? pw.h16_grid : kH16Grid;  // "h16_grid"
   const uint32_t grid = std::min<uint32_t>((n + 255) / 256, gmax);
   uint32_t segcap = (pw.cap / 2) / grid;  // 16-B fix-up entries per workgroup
   if (pw.segcap) segcap = std::min(segcap, pw.segcap);  // "h16_segcap" (tests: the in-place path)
@@ -930,7 +930,7 @@ int launch_project(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_
       // option "wide_grid": one resident round (2 workgroups of 6 waves per CU): C5 projection
       // 1203 -> 1076 ms per step (256..8192 swept on one box: 256 -> 1073, 512 -> 1076, 1024 ->
       // 1112, 2048 -> 1203, 4096 -> 1318, 8192 -> 1533)
-      const uint32_t wcap = pw->wide_grid ? std::max(64u, pw->wide_grid) : 512u;
+      const uint32_t wcap = pw->wide_grid ? pw->wide_grid : 512u;
       const dim3 gm(std::min<uint32_t>(groups, wcap));
       // stamped as one span: the screen (start) and the fix-up of its close calls (end)
       KTime k1 = kt;
@@ -943,7 +943,7 @@ int launch_project(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_
         k_project_mfma_wide<0><<<gm, dim3(kWideNT), lds, s>>>(r.x, r.d, r.dp, slots, keys, n, W, h,
                                                               key_or, wide_eps(r.d), wide_abs(r.d),
                                                               *pw, kt);
-      const uint32_t fcap = pw->fix_grid ? std::max(16u, pw->fix_grid) : 1024u;  // "fix_grid"
+      const uint32_t fcap = pw->fix_grid ? pw->fix_grid : 1024u;  // "fix_grid"
       k_project_fix<<<fcap, block, flds, s>>>(r.x, r.d, r.dp, slots, keys, W, h, *pw, k1);
       return kPkWide;
     }

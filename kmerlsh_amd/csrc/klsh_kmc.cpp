@@ -409,7 +409,8 @@ class KmcFileSource : public klsh::KhSource {
       return set_error(KLSH_E_ARG, (db.suf + ": short file").c_str());
     st_.io_ms += now_ms() - tio;
     KLSH_KRET(hipMemcpyAsync(drec_, hrec_.data(), n * kp_.rec_size, hipMemcpyHostToDevice, s));
-    klsh::launch_kmc_decode(drec_, n, r0, kp_, dlut_, db.lut.size(), drep_, dcnt_, nvalid_, s);
+    klsh::launch_kmc_decode(drec_, n, r0, kp_, dlut_, db.lut.size(), drep_, dcnt_, nvalid_, s,
+                            hooks_.grid_cap);
     if (pass == 0) ++hooks_.decode_launches;
     *rep = drep_;
     *cnt = dcnt_;
@@ -458,6 +459,7 @@ int klsh::khtable_run(klsh_ctx* ctx, klsh::KhSource& src, int n_samples, int k, 
                       klsh_khtable_stats* st) {
   klsh_khtable_stats& local = *st;
   klsh::KmcHooks& hooks = klsh::ctx_kmc(ctx);
+  const uint32_t gc = hooks.grid_cap;  // option "grid_cap" (tests): workgroups per launch, at most
   const hipStream_t s = klsh::ctx_stream(ctx);
   const std::string dir = (out_dir && *out_dir) ? std::string(out_dir) + "/" : std::string();
   uint64_t records = 0;
@@ -495,8 +497,8 @@ int klsh::khtable_run(klsh_ctx* ctx, klsh::KhSource& src, int n_samples, int k, 
         const uint64_t* drep = nullptr;
         const uint32_t* dcnt = nullptr;
         if ((rc = src.feed(j, pass, r0, n, &drep, &dcnt, s))) goto done;
-        if (pass == 0) klsh::launch_kmc_union(drep, n, base[j] + r0, tab, first, mask, s);
-        else klsh::launch_kmc_count(drep, dcnt, n, tab, mask, acc, s);
+        if (pass == 0) klsh::launch_kmc_union(drep, n, base[j] + r0, tab, first, mask, s, gc);
+        else klsh::launch_kmc_count(drep, dcnt, n, tab, mask, acc, s, gc);
         KLSH_KHIP(hipGetLastError());
         src.fed(j, pass, n);
         KLSH_KHIP(hipStreamSynchronize(s));  // the source reuses its buffers for the next chunk
@@ -509,14 +511,14 @@ int klsh::khtable_run(klsh_ctx* ctx, klsh::KhSource& src, int n_samples, int k, 
         if (nv < total) {
           const uint64_t zero = 0;
           KLSH_KHIP(hipMemcpyAsync(dzero, &zero, 8, hipMemcpyHostToDevice, s));
-          klsh::launch_kmc_union(dzero, 1, base[j] + total, tab, first, mask, s);
+          klsh::launch_kmc_union(dzero, 1, base[j] + total, tab, first, mask, s, gc);
           KLSH_KHIP(hipGetLastError());
           KLSH_KHIP(hipStreamSynchronize(s));
         }
         base[j + 1] = base[j] + total + 1;
       } else {
         // this sample's column in output order (WriteHT, io/ioHT.cc:30-55)
-        klsh::launch_kmc_emit(acc, slots, kmap, col, s);
+        klsh::launch_kmc_emit(acc, slots, kmap, col, s, gc);
         KLSH_KHIP(hipGetLastError());
         std::vector<uint16_t> hcol(kmap);
         if (kmap) KLSH_KHIP(hipMemcpyAsync(hcol.data(), col, kmap * 2ull, hipMemcpyDeviceToHost, s));
@@ -536,7 +538,7 @@ int klsh::khtable_run(klsh_ctx* ctx, klsh::KhSource& src, int n_samples, int k, 
       KLSH_KHIP(hipMalloc((void**)&slots2, (cap / 2 + 64) * 4));
       KLSH_KHIP(hipMalloc((void**)&ws, klsh::sort_ws_words(cap / 2 + 64) * 4));
       KLSH_KHIP(hipMemsetAsync(nvalid, 0, 4, s));
-      klsh::launch_kmc_collect(tab, first, cap, lo, slots, nvalid, s);
+      klsh::launch_kmc_collect(tab, first, cap, lo, slots, nvalid, s, gc);
       KLSH_KHIP(hipGetLastError());
       KLSH_KHIP(hipMemcpyAsync(&kmap, nvalid, 4, hipMemcpyDeviceToHost, s));
       KLSH_KHIP(hipStreamSynchronize(s));
@@ -549,7 +551,7 @@ int klsh::khtable_run(klsh_ctx* ctx, klsh::KhSource& src, int n_samples, int k, 
         hooks.high_sort = 1;
         uint32_t* hk = ok_ == lo ? lo2 : lo;  // the free key buffer
         uint32_t* hv = ov_ == slots ? slots2 : slots;
-        klsh::launch_kmc_hi(first, ov_, kmap, hk, s);
+        klsh::launch_kmc_hi(first, ov_, kmap, hk, s, gc);
         uint32_t *ok2 = nullptr, *ov2 = nullptr;
         klsh::radix_sort(hk, ov_, ok_, hv, kmap, hbits, ws, &ok2, &ov2, s);
         ov_ = ov2;
@@ -558,7 +560,7 @@ int klsh::khtable_run(klsh_ctx* ctx, klsh::KhSource& src, int n_samples, int k, 
       if (ov_ != slots) KLSH_KHIP(hipMemcpyAsync(slots, ov_, kmap * 4ull, hipMemcpyDeviceToDevice, s));
       KLSH_KHIP(hipMalloc((void**)&keys_out, (uint64_t)std::max<uint32_t>(kmap, 1) * 8));
       KLSH_KHIP(hipMalloc((void**)&col, (uint64_t)std::max<uint32_t>(kmap, 1) * 2));
-      klsh::launch_kmc_emit_keys(tab, slots, kmap, keys_out, s);
+      klsh::launch_kmc_emit_keys(tab, slots, kmap, keys_out, s, gc);
       KLSH_KHIP(hipGetLastError());
       std::vector<uint64_t> hkeys(kmap);
       std::vector<uint32_t> hslots(kmap);

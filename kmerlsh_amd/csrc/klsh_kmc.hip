@@ -159,41 +159,44 @@ __global__ __launch_bounds__(256) void k_kmc_emit(const uint32_t* __restrict__ a
     out[i] = (uint16_t)min(acc[order[i]], 65535u);
 }
 
-static uint32_t grid_for(uint64_t n) {
+static uint32_t grid_for(uint64_t n, uint32_t grid_cap) {
   const uint64_t g = (n + 255) / 256;
-  return (uint32_t)(g < 16384 ? (g ? g : 1) : 16384);
+  return cap_grid((uint32_t)(g < 16384 ? (g ? g : 1) : 16384), grid_cap);
 }
 
 void launch_kmc_decode(const uint8_t* recs, uint64_t n, uint64_t rec0, const KmcParams& kp,
                        const uint64_t* lut, uint64_t lut_n, uint64_t* rep, uint32_t* cnt,
-                       uint32_t* n_valid, hipStream_t s) {
-  if (n) k_kmc_decode<<<grid_for(n), 256, 0, s>>>(recs, n, rec0, kp, lut, lut_n, rep, cnt, n_valid);
+                       uint32_t* n_valid, hipStream_t s, uint32_t grid_cap) {
+  if (n)
+    k_kmc_decode<<<grid_for(n, grid_cap), 256, 0, s>>>(recs, n, rec0, kp, lut, lut_n, rep, cnt,
+                                                       n_valid);
 }
 void launch_kmc_union(const uint64_t* rep, uint64_t n, uint64_t ord0, uint64_t* tab,
-                      uint64_t* first, uint64_t mask, hipStream_t s) {
+                      uint64_t* first, uint64_t mask, hipStream_t s, uint32_t grid_cap) {
   if (n)
-    k_kmc_union<<<grid_for(n), 256, 0, s>>>(rep, n, ord0, reinterpret_cast<unsigned long long*>(tab),
-                                            reinterpret_cast<unsigned long long*>(first), mask);
+    k_kmc_union<<<grid_for(n, grid_cap), 256, 0, s>>>(
+        rep, n, ord0, reinterpret_cast<unsigned long long*>(tab),
+        reinterpret_cast<unsigned long long*>(first), mask);
 }
 void launch_kmc_count(const uint64_t* rep, const uint32_t* cnt, uint64_t n, const uint64_t* tab,
-                      uint64_t mask, uint32_t* acc, hipStream_t s) {
-  if (n) k_kmc_count<<<grid_for(n), 256, 0, s>>>(rep, cnt, n, tab, mask, acc);
+                      uint64_t mask, uint32_t* acc, hipStream_t s, uint32_t grid_cap) {
+  if (n) k_kmc_count<<<grid_for(n, grid_cap), 256, 0, s>>>(rep, cnt, n, tab, mask, acc);
 }
 void launch_kmc_collect(const uint64_t* tab, const uint64_t* first, uint64_t cap, uint32_t* lo,
-                        uint32_t* slot, uint32_t* n_out, hipStream_t s) {
-  k_kmc_collect<<<grid_for(cap), 256, 0, s>>>(tab, first, cap, lo, slot, n_out);
+                        uint32_t* slot, uint32_t* n_out, hipStream_t s, uint32_t grid_cap) {
+  k_kmc_collect<<<grid_for(cap, grid_cap), 256, 0, s>>>(tab, first, cap, lo, slot, n_out);
 }
 void launch_kmc_hi(const uint64_t* first, const uint32_t* slots, uint64_t n, uint32_t* hi,
-                   hipStream_t s) {
-  if (n) k_kmc_hi<<<grid_for(n), 256, 0, s>>>(first, slots, n, hi);
+                   hipStream_t s, uint32_t grid_cap) {
+  if (n) k_kmc_hi<<<grid_for(n, grid_cap), 256, 0, s>>>(first, slots, n, hi);
 }
 void launch_kmc_emit_keys(const uint64_t* tab, const uint32_t* order, uint64_t n, uint64_t* out,
-                          hipStream_t s) {
-  if (n) k_kmc_emit_keys<<<grid_for(n), 256, 0, s>>>(tab, order, n, out);
+                          hipStream_t s, uint32_t grid_cap) {
+  if (n) k_kmc_emit_keys<<<grid_for(n, grid_cap), 256, 0, s>>>(tab, order, n, out);
 }
 void launch_kmc_emit(const uint32_t* acc, const uint32_t* order, uint64_t n, uint16_t* out,
-                     hipStream_t s) {
-  if (n) k_kmc_emit<<<grid_for(n), 256, 0, s>>>(acc, order, n, out);
+                     hipStream_t s, uint32_t grid_cap) {
+  if (n) k_kmc_emit<<<grid_for(n, grid_cap), 256, 0, s>>>(acc, order, n, out);
 }
 
 }  // namespace klsh

@@ -3420,7 +3420,8 @@ static void launch_huge(const MergeWork& w, uint32_t* slots, const Decider& dc, 
       return ok;
     }();
     (void)lds_ok;
-    g = std::min(g, w.long_groups);
+    // (the matrices stay sized for long_groups workgroups; "grid_cap" only leaves some unused)
+    g = cap_grid(std::min(g, w.long_groups), w.grid_cap);
     const uint2* l2 = with896 ? w.big[kBigClasses - 1] : nullptr;
     const uint32_t* c2 = &w.rc->n_big[kBigClasses - 1].v;
     if (r.d == 16)
@@ -3429,6 +3430,7 @@ static void launch_huge(const MergeWork& w, uint32_t* slots, const Decider& dc, 
       k_merge_long<32><<<g, kLongNT, lds, s>>>(w.huge, &w.rc->n_huge.v, l2, c2, slots, dc, r, w, ctr);
     return;
   }
+  g = cap_grid(g, w.grid_cap);
   const size_t lds = huge_lds(r.d, r.dp, kHugeNT);
   static const bool lds_ok = [] {
     bool ok = true;
@@ -3914,7 +3916,7 @@ static void launch_big(const MergeWork& w, int c, uint32_t* slots, const Decider
   }();
   (void)lds_ok;
   const uint32_t lo = c == 0 ? 65u : (uint32_t)kBigRows[c - 1] + 1u;
-  const uint32_t g = (uint32_t)std::min<uint64_t>(1024, n / lo + 1);
+  const uint32_t g = cap_grid((uint32_t)std::min<uint64_t>(1024, n / lo + 1), w.grid_cap);
   k_merge_big<D, RB, NT, ROWS_LDS><<<g, NT, lds, s>>>(w, c, slots, dc, r, ctr);
 }
 
@@ -3963,7 +3965,7 @@ static bool screen_ok(const Rows& r, const Decider& dc, const MergeWork& w) {
 
 // The small-run merge's persistent launch (option "small_grid"; default 12288).
 static uint32_t small_grid(const MergeWork& w) {
-  return w.small_grid ? std::max(256u, w.small_grid) : 12288u;
+  return w.small_grid ? w.small_grid : 12288u;
 }
 
 // Iterations below this many positions run every merge class in ONE launch (k_merge_tail) on the
@@ -4002,7 +4004,7 @@ static void launch_groups(const Rows& r, uint32_t* slots, const Decider& dc, con
       screen_margins(r.d, &m0, &a2);
       // (option tail_screen_grid; one box, interleaved C2: 512 → 214.9, 1024 → 210.0, 2048 →
       // 208.1 ms per step; tail_screen = 0: 213.3 ms)
-      const uint32_t sgrid = w.tail_screen_grid ? std::max(64u, w.tail_screen_grid) : 2048u;
+      const uint32_t sgrid = w.tail_screen_grid ? w.tail_screen_grid : 2048u;
       k_small_screen<D><<<sgrid, 64, 0, s>>>(w, slots, r, dc.s_star, m0, a2, w.kt);
       wt.screened = 1u;
     }
@@ -4047,7 +4049,7 @@ static void launch_groups(const Rows& r, uint32_t* slots, const Decider& dc, con
     screen_margins(r.d, &m0, &a2);
     // (option small_screen_grid; one-wave workgroups: 2048 → 207.9 / 207.8 vs 3072 → 211.2 /
     // 211.1 ms per C2 step on one box, 1024 → 227–228, 1536 / 2560 within noise of 2048)
-    const uint32_t sgrid = w.screen_grid ? std::max(64u, w.screen_grid) : 2048u;
+    const uint32_t sgrid = w.screen_grid ? w.screen_grid : 2048u;
     k_small_screen<D><<<sgrid, 64, 0, s_small>>>(w, slots, r, dc.s_star, m0, a2, w.kt);
     MergeWork ws = w;
     ws.screened = 1u;
@@ -4073,7 +4075,7 @@ static void launch_big_wide(const MergeWork& w, int c, uint32_t* slots, const De
   }();
   (void)lds_ok;
   const uint32_t lo = c == 0 ? 65u : (uint32_t)kBigRows[c - 1] + 1u;
-  const uint32_t g = (uint32_t)std::min<uint64_t>(1024, n / lo + 1);
+  const uint32_t g = cap_grid((uint32_t)std::min<uint64_t>(1024, n / lo + 1), w.grid_cap);
   k_merge_big_wide<RB, NT, KC><<<g, NT, lds, s>>>(w, c, slots, dc, r, ctr);
 }
 
@@ -4094,7 +4096,7 @@ static void launch_groups_wide(const Rows& r, uint32_t* slots, const Decider& dc
     // step, interleaved on one box), as for the register-row small-run launch
     // option "wide_group_grid": 4096 -> 1221, 8192 -> 1141, 16384 -> 1103, 32768 -> 1102 ms
     // per C5 step (one box)
-    const uint64_t cap = w.wide_group_grid ? std::max(64u, w.wide_group_grid) : 16384u;
+    const uint64_t cap = w.wide_group_grid ? w.wide_group_grid : 16384u;
     return (uint32_t)std::min<uint64_t>(cap, group_class_capacity(c, n) / per_wave + 1);
   };
   const Fork f(w, s);

@@ -22,10 +22,10 @@ __global__ __launch_bounds__(256) void k_bin_hist(const uint32_t* __restrict__ k
 }
 
 void launch_bin_hist(const uint32_t* keys, uint32_t n, int shift, uint32_t nbins, uint32_t* hist,
-                     hipStream_t s) {
+                     hipStream_t s, uint32_t grid_cap) {
   (void)hipMemsetAsync(hist, 0, sizeof(uint32_t) * nbins, s);
   if (n == 0) return;
-  const uint32_t g = (uint32_t)std::min<uint64_t>(1024, (n + 255) / 256);
+  const uint32_t g = cap_grid((uint32_t)std::min<uint64_t>(1024, (n + 255) / 256), grid_cap);
   k_bin_hist<<<g, 256, 0, s>>>(keys, n, shift, nbins, hist);
 }
 
@@ -287,11 +287,12 @@ __global__ __launch_bounds__(256) void k_delta_pack(Rows r, const uint32_t* __re
 }
 
 void launch_delta_pack(const Rows& r, const uint32_t* delta_slots, uint32_t n, uint32_t* rec,
-                       hipStream_t s) {
+                       hipStream_t s, uint32_t grid_cap) {
   const uint64_t total = (uint64_t)n * (uint64_t)delta_words(r.dp);
   if (total)
-    k_delta_pack<<<(unsigned)std::min<uint64_t>((total + 255) / 256, kDeltaGrid), 256, 0, s>>>(
-        r, delta_slots, n, rec);
+    k_delta_pack<<<cap_grid((uint32_t)std::min<uint64_t>((total + 255) / 256, kDeltaGrid),
+                            grid_cap),
+                   256, 0, s>>>(r, delta_slots, n, rec);
 }
 
 __global__ __launch_bounds__(256) void k_delta_apply(Rows r, const uint32_t* __restrict__ rec,
@@ -339,11 +340,13 @@ void launch_publish_words(const uint32_t* a, uint32_t na, const uint32_t* b, uin
   k_publish_words<<<1, 256, 0, s>>>(a, na, b, nb, dst, seq_host, seq);
 }
 
-void launch_delta_apply(const Rows& r, const uint32_t* rec, uint32_t n, hipStream_t s) {
+void launch_delta_apply(const Rows& r, const uint32_t* rec, uint32_t n, hipStream_t s,
+                        uint32_t grid_cap) {
   const uint64_t total = (uint64_t)n * (uint64_t)delta_words(r.dp);
   if (total)
-    k_delta_apply<<<(unsigned)std::min<uint64_t>((total + 255) / 256, kDeltaGrid), 256, 0, s>>>(
-        r, rec, n);
+    k_delta_apply<<<cap_grid((uint32_t)std::min<uint64_t>((total + 255) / 256, kDeltaGrid),
+                             grid_cap),
+                    256, 0, s>>>(r, rec, n);
 }
 
 __global__ __launch_bounds__(256) void k_min_u32(uint32_t* __restrict__ a,

@@ -9,10 +9,24 @@ switch and the sharded delta apply write that state in their own code; `assert_r
 it back through the klsh_row_state hook and compares it, by bits, with what the returned rows and
 offsets say it must be.  No tolerances: a cache that is off by one ulp is a wrong cache.
 
-Also here: the seeded inputs of the state tests ("spread" single-bucket rows, "ladder" loop rows)
-and the options context manager, shared by test_gpu_row_state.py and test_gpu_sharded.py.
+Also here: the seeded inputs of the state tests ("spread" single-bucket rows, "ladder" loop rows),
+the projection tests' adversarial rows, the result comparison and the options context manager,
+shared by test_gpu_parity.py, test_gpu_row_state.py, test_gpu_sharded.py and
+test_gpu_launch_geometry.py.
 """
 import numpy as np
+
+
+def same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32),
+                          np.ascontiguousarray(b, np.float32).view(np.uint32))
+
+
+def assert_same_result(got, rows, off, ids):
+    g_rows, g_off, g_ids = got
+    assert np.array_equal(g_off, off)
+    assert np.array_equal(g_ids, ids)
+    assert same_bits(g_rows, rows)
 
 
 def seq_norms(rows):
@@ -76,6 +90,16 @@ def check_state(st, rows, off, what=""):
     assert st["pad_nonzero"] == 0, f"{what}: {st['pad_nonzero']} pad words are not +0"
     assert st["bad_links"] == 0, f"{what}: {st['bad_links']} member chains do not match cnt / tail"
     return st
+
+
+def check(engine, want, what):
+    """Result against the oracle's (rows, off, ids), then the cached state against the result."""
+    got = engine.result()
+    try:
+        assert_same_result(got, *want[:3])
+    except AssertionError as ex:
+        raise AssertionError(f"result differs: {what}") from ex
+    return assert_row_state(engine, got[0], got[1], what)
 
 
 def same_state(a, b):
@@ -191,3 +215,50 @@ def ladder(n, d, special=False):
             else:
                 rows[i] *= np.float32([1e30, 1e-30, 1e5, 1e-9][kind % 6 - 2])
     return rows, off, ids
+
+
+def adversarial_rows(rng, n, d, w):
+    """Rows the certified projection screens cannot call, and rows that break the fp16 image:
+    every third row projected onto hyperplane i % h (s is rounding noise around 0), rows whose
+    sequential sum is exactly 0 for a hyperplane (x = w_l e_k - w_k e_l: the two products are
+    exact negatives), zero / -0 / tiny / huge / NaN / inf rows, elements past fp16's range
+    (>= 65520 -> inf in the image), fp16-subnormal rows and rows whose fp16 image is all zero
+    while the f32 row is not, f32-subnormal rows."""
+    h = w.shape[0]
+    w64 = w.astype(np.float64)
+    rows = rng.normal(0, 1, size=(n, d))
+    for i in range(0, n, 3):
+        j = i % h
+        rows[i] -= (rows[i] @ w64[j]) / (w64[j] @ w64[j]) * w64[j]
+    rows = rows.astype(np.float32)
+    f = np.float32
+    rows[1] = 0.0
+    rows[4] *= f(1e-30)
+    rows[7] *= f(1e30)
+    rows[10, 3] = np.nan
+    rows[13] = -0.0
+    for m, i in enumerate(range(2, min(n, 2 + 3 * h * 4), 3)):  # s == 0 exactly for hyperplane j
+        j, k = m % h, (m * 7) % d
+        l = (k + 1 + m % (d - 1)) % d if d > 1 else k
+        if l == k:
+            continue
+        rows[i] = 0.0
+        rows[i, k], rows[i, l] = w[j, l], -w[j, k]
+        if m % 2:
+            rows[i] *= f(-1)
+    special = {
+        16: lambda r: r.__setitem__(0, f(70000.0)),      # fp16 overflow: inf in the image
+        19: lambda r: r.__setitem__(d - 1, f(65519.0)),  # rounds to 65504, finite
+        22: lambda r: r.__imul__(f(1e-6)),               # fp16 subnormal image
+        25: lambda r: r.__imul__(f(1e-9)),               # fp16 image all zero, f32 nonzero
+        28: lambda r: r.__setitem__(slice(0, d // 2), r[: d // 2] * f(1e-9)),
+        31: lambda r: r.__setitem__(slice(None), np.where(np.arange(d) % 2, f(-0.0), f(0.0))),
+        34: lambda r: r.__setitem__(0, f(np.inf)),
+        37: lambda r: r.__imul__(f(1e-40)),              # f32 subnormal
+        40: lambda r: r.__setitem__(slice(None), f(65504.0)),
+        43: lambda r: r.__setitem__(d // 2, f(-1e5)),
+    }
+    for i, fn in special.items():
+        if i < n:
+            fn(rows[i])
+    return rows

@@ -12,32 +12,10 @@ import numpy as np
 import pytest
 
 import row_state
-from row_state import (LADDER_CALL, LADDER_SHAPES, assert_row_state, ladder_reference, options,
-                       same_state, spread_cached)
+from row_state import (LADDER_CALL, LADDER_SHAPES, assert_row_state, check, ladder_reference,
+                       options, same_state, spread_cached)
 
 pytestmark = pytest.mark.gpu
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32),
-                          np.ascontiguousarray(b, np.float32).view(np.uint32))
-
-
-def assert_same_result(got, rows, off, ids):
-    g_rows, g_off, g_ids = got
-    assert np.array_equal(g_off, off)
-    assert np.array_equal(g_ids, ids)
-    assert same_bits(g_rows, rows)
-
-
-def check(engine, want, what):
-    """Result against the oracle's (rows, off, ids), then the cached state against the result."""
-    got = engine.result()
-    try:
-        assert_same_result(got, *want[:3])
-    except AssertionError as ex:
-        raise AssertionError(f"result differs: {what}") from ex
-    return assert_row_state(engine, got[0], got[1], what)
 
 
 # ------------------------------------------------------------------------------ shapes ---------
