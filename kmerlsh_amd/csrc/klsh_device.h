@@ -1,4 +1,5 @@
-// Device helpers shared by the gfx950 kernels (klsh_kernels.hip, klsh_merge.hip).
+// Device helpers shared by the gfx950 kernels (klsh_kernels.hip, and klsh_merge.hip's
+// kernel headers klsh_merge_*.h).
 // Numerics contract: see klsh_kernels.hip (sequential fp32, no FMA, IEEE sqrt/div).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -5,6 +5,8 @@ by source line — each one a memory round trip of its own (the
       --cuda-device-only -S klsh_merge.hip -o /tmp/m.s
   python tools/isa_waits.py /tmp/m.s [top N] [kernel-name substring]
 
+klsh_merge.hip is one translation unit over the klsh_merge_*.h headers, where its kernels are: a
+location prints as header:line (klsh_merge_big.h:412).
 Without -gline-tables-only the source lines print as None.  Loads that must wait (a pointer
 chase, a spin) show up too: read the line before changing it.
 """
