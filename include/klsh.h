@@ -212,6 +212,9 @@ int klsh_comm_info(klsh_ctx* ctx, int* rank, int* world);
  *                      small sizes).  Iterations below min(this, 2^20) rows are also queued
  *                      several at a time (one host sync per batch)
  *   "h16_segcap" (tests) caps the fp16 projection's per-workgroup fix-up segment.
+ *   "h16_bound"        1 (default) = the fp16 projection (d = 16, 32, 64) certifies a sign against
+ *                      eps * sum_k |x_k||w_k| (a third MFMA per k-step); 0 = against eps * |x||w|,
+ *                      which leaves ~1.6x as many pairs to the exact chains.  Same keys either way
  *   "long_runs"        4 (default) = runs over 384 rows at d = 16 / 32 through k_merge_long
  *                      (Gram bit matrix + one walk step per merge); 1 = only runs over 896 rows;
  *                      0 = k_merge_huge for those

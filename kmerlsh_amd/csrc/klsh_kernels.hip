@@ -289,18 +289,37 @@ typedef float pf32x16 __attribute__((ext_vector_type(16)));
 //                                 subnormal) and the MFMA's f32 sums, (17 + 2 ceil(d/16)) 2^-23
 //            + |x~.w - x.w|      fp16 rounding of x: 2^-11 |x_k| (+ 2^-25 absolute, subnormals)
 //            + |x.w - s|         the reference's own (d + 1) 2^-24
-// summed over k with Cauchy-Schwarz: <= eps |w||x| + abs_c (|w| + |x~|) (h16_eps / h16_abs, with
-// 1.5x headroom; |x| <= 1.001 |x~| covers the 2^-11).  Signs with |S| above the bound are the
-// reference's bits; the rest (fp16 overflow, NaN, |S| within the bound: ~0.5 % of the
-// row-hyperplane pairs at d = 64) go to the fix-up list (k_project_fix: the exact chains on the
-// f32 row).  32 rows x 32 hyperplanes per MFMA tile; the next group's rows are loaded during the
-// current group.
+// Every relative term is a per-element error times |x_k||w_k|, so the sum over k is bounded by
+// eps T, T = sum_k |x_k||w_k|, and T by a third MFMA per k-step, T~ = |w_hi| . |x~| (option
+// "h16_bound" = 1, the default; 0 bounds T by Cauchy-Schwarz, |w||x|, which calls ~1.6x fewer
+// pairs).  With T' = sum_k |x~_k||w_hi,k| (exact) and fp16 round-to-nearest, |v - fp16(v)| <=
+// 2^-11 |fp16(v)| for a normal image (half an ulp of the image's binade), hence |x_k| <=
+// (1 + 2^-11) |x~_k| and |w_k| <= (1 + 2^-11) |w_hi,k| <= (1 + 2^-10) |w_hi,k|:
+//   fp16 rounding of x   sum |x_k - x~_k||w_k|              <= 2^-11 (1 + 2^-10) T'
+//   w_lo residual        sum |x~_k||w_k - w_hi,k - w_lo,k|  <= 2^-22 T'   (|w - w_hi| <= 2^-11 |w_hi|,
+//                                                              rounded to fp16 once more)
+//   MFMA sums of S       (17 + 2 ceil(d/16)) 2^-23 sum |x~_k|(|w_hi,k| + |w_lo,k|)
+//                                                           <= (17 + 2 ceil(d/16)) 2^-23 (1 + 2^-11) T'
+//   the reference's own  (d + 1) 2^-24 sum |x_k||w_k|       <= (d + 1) 2^-24 (1 + 2^-11)(1 + 2^-10) T'
+//   MFMA sums of T~      positive terms, one MFMA per k-step: T~ >= (1 - (17 + ceil(d/16)) 2^-23) T',
+//                        T' <= (1 + 2^-18) T~ at d <= 64
+// so |S - s| <= eps_T T~ + abs_c (|w| + |x~|), eps_T = h16_eps(d) (1 + 2^-9): the same sum of
+// constants as the norm bound's, with the same 1.5x headroom, and (1 + 2^-9) > (1 + 2^-10)
+// (1 + 2^-11)(1 + 2^-18) over all the factors above.  The absolute term is unchanged: elements
+// whose image is subnormal (x~_k, w_hi,k or w_lo,k: off by <= 2^-25 each) add at most 2^-25
+// sqrt(d) (|w| + |x~|), and what the same elements take from T~ is eps_T times that, inside the
+// headroom.  A non-finite S or T~ is never called.
+// Signs with |S| above the bound are the reference's bits; the rest (fp16 overflow, NaN, |S|
+// within the bound: ~0.3 % of the row-hyperplane pairs at d = 64, ~0.5 % under the norm bound) go
+// to the workgroup's fix-up segment (the exact chains on the f32 row).  32 rows x 32 hyperplanes
+// per MFMA tile; the next group's rows are loaded during the current group.
 typedef _Float16 ph16x8 __attribute__((ext_vector_type(8)));
 
 float h16_eps(int d) {
   const float ks = (float)((d + 15) / 16);
   return 1.5f * (0x1p-11f + 0x1p-22f + (17.0f + 2.0f * ks) * 0x1p-23f + (float)(d + 1) * 0x1p-24f);
 }
+float h16_eps_t(int d) { return h16_eps(d) * (1.0f + 0x1p-9f); }  // against T~ (see above)
 float h16_abs(int d) { return 1.5f * 2.0f * 0x1p-25f * std::sqrt((float)d); }
 
 // Lane-owned rows: every lane loads one whole fp16 row (2d bytes), then one v_permlane32_swap per
@@ -325,7 +344,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
                                                      const uint32_t* __restrict__ n_dev,
                                                      const uint32_t* __restrict__ woff_dev) {
   constexpr int KS = D / 16;  // k-steps of 16 columns
-  __shared__ ph16x8 sa[2][KS][64];  // A fragments (w_hi, w_lo) of every lane, per k-step
+  __shared__ ph16x8 sa[3][KS][64];  // A fragments (w_hi, w_lo, |w_hi|) of every lane, per k-step
   __shared__ __attribute__((aligned(16))) float swf[32 * D];  // f32 hyperplanes (exact chains)
   __shared__ float swn[32];         // |w_j| (bounds)
   __shared__ uint32_t s_cnt;        // entries of this workgroup's fix-up segment
@@ -358,10 +377,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     const int e = (int)t + 256 * i, j = e / D, k = e % D;
     wl[i] = W[(size_t)(j < h ? j : 0) * dp + k];
   }
-  const uint32_t sl0 = slots[g0 + lane < n ? g0 + lane : 0u];
+  uint32_t sl = slots[g0 + lane < n ? g0 + lane : 0u];  // the slot of the lane's row
   __builtin_amdgcn_sched_barrier(0);  // (keeps every hyperplane load ahead of the row loads)
   ph16x8 xr[2 * KS];  // the lane's row, 8 columns per chunk
-  load_rows(xr, sl0);
+  load_rows(xr, sl);
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int i = 0; i < NWL; ++i) {
@@ -383,20 +402,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
   // A fragment of lane L at k-step s: hyperplane L & 31, columns 16s + 8(L >> 5) + 0..7, split
   for (int e = (int)t; e < KS * 64; e += 256) {
     const int sk = e >> 6, L = e & 63, j = L & 31, k0 = 16 * sk + 8 * (L >> 5);
-    ph16x8 hi8, lo8;
+    ph16x8 hi8, lo8, ab8;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const float w = swf[j * D + k0 + q];
       const _Float16 hi = (_Float16)w;
       hi8[q] = hi;
       lo8[q] = (_Float16)(w - (float)hi);  // w - hi is exact in f32
+      ab8[q] = __builtin_fabsf16(hi);
     }
     sa[0][sk][L] = hi8;
     sa[1][sk][L] = lo8;
+    sa[2][sk][L] = ab8;
   }
   __syncthreads();
   uint4* seg = reinterpret_cast<uint4*>(pw.fix) + (size_t)blockIdx.x * segcap;
-  auto group = [&](const ph16x8 (&xr)[2 * KS], uint32_t g0) __attribute__((always_inline)) {
+  // the value of lane L ^ 32 (one v_permlane32_swap: no lane-address registers held over the loop)
+  auto xor32 = [&](uint32_t v) __attribute__((always_inline)) {
+    auto p = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    return hh ? p[0] : p[1];
+  };
+  // one loop for both bounds: |S| > eps_t T~ + |w_j| (eps_n |x~| + abs_c) + abs_c |x~|, with
+  // eps_n = 0 under the T bound and eps_t = 0 (and no third MFMA) under the norm bound
+  const bool tbound = pw.h16_cs == 0u;  // "h16_bound"
+  const float eps_t = tbound ? eps : 0.0f, eps_n = tbound ? 0.0f : eps;
+  auto group = [&](ph16x8 (&xr)[2 * KS], uint32_t g0, uint32_t slot) __attribute__((always_inline)) {
+    // the fragments are read from LDS in every group: kept in registers across groups (the
+    // compiler hoists the reads: 48 registers at d = 64), the kernel spills
+    asm volatile("" ::: "memory");
     float ss = 0.0f;  // |x~|^2 of the lane's row (a bound only)
 #pragma unroll
     for (int c = 0; c < 2 * KS; ++c)
@@ -406,49 +439,67 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
         ss = __builtin_amdgcn_fdot2(v, v, ss, false);
       }
     const float xn = __builtin_amdgcn_sqrtf(ss) * 1.001f;  // >= |x| (or inf / NaN)
-    pf32x16 accA, accB;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) accA[i] = accB[i] = 0.0f;
+    const float xo = __uint_as_float(xor32(__float_as_uint(xn)));
+    // B operands, in place: xr[2s] becomes tile A's (rows of lanes 0-31), xr[2s + 1] tile B's
+    // (rows of lanes 32-63)
 #pragma unroll
     for (int sk = 0; sk < KS; ++sk) {
-      uint4 a = *reinterpret_cast<const uint4*>(&xr[2 * sk]);
-      uint4 b = *reinterpret_cast<const uint4*>(&xr[2 * sk + 1]);
+      const uint4 a = *reinterpret_cast<const uint4*>(&xr[2 * sk]);
+      const uint4 b = *reinterpret_cast<const uint4*>(&xr[2 * sk + 1]);
       auto p0 = __builtin_amdgcn_permlane32_swap(a.x, b.x, false, false);
       auto p1 = __builtin_amdgcn_permlane32_swap(a.y, b.y, false, false);
       auto p2 = __builtin_amdgcn_permlane32_swap(a.z, b.z, false, false);
       auto p3 = __builtin_amdgcn_permlane32_swap(a.w, b.w, false, false);
-      a = make_uint4(p0[0], p1[0], p2[0], p3[0]);  // tile A (rows of lanes 0-31)
-      b = make_uint4(p0[1], p1[1], p2[1], p3[1]);  // tile B (rows of lanes 32-63)
-      const ph16x8 fa = *reinterpret_cast<const ph16x8*>(&a);
-      const ph16x8 fb = *reinterpret_cast<const ph16x8*>(&b);
-      const ph16x8 wh = sa[0][sk][lane], wl = sa[1][sk][lane];
-      accA = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, fa, accA, 0, 0, 0);
-      accB = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, fb, accB, 0, 0, 0);
-      accA = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, fa, accA, 0, 0, 0);
-      accB = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, fb, accB, 0, 0, 0);
+      *reinterpret_cast<uint4*>(&xr[2 * sk]) = make_uint4(p0[0], p1[0], p2[0], p3[0]);
+      *reinterpret_cast<uint4*>(&xr[2 * sk + 1]) = make_uint4(p0[1], p1[1], p2[1], p3[1]);
     }
+    // S and T~ of tile A and its bits, then tile B: two accumulator tiles live, not four.
     // acc[i] = S[hyperplane (i&3) + 8(i>>2) + 4hh][tile row lane & 31]; tile A's row R is lane
     // R's own, tile B's lane 32 + R's
-    const float xo = __shfl_xor(xn, 32, 64);
     uint32_t bits[2], amb[2];
 #pragma unroll
     for (int tb = 0; tb < 2; ++tb) {
+      pf32x16 accS, accT;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) accS[i] = accT[i] = 0.0f;
+      if (tbound) {
+#pragma unroll
+        for (int sk = 0; sk < KS; ++sk) {
+          uint4 u = *reinterpret_cast<const uint4*>(&xr[2 * sk + tb]);
+          const ph16x8 fx = *reinterpret_cast<const ph16x8*>(&u);
+          u.x &= 0x7fff7fffu;
+          u.y &= 0x7fff7fffu;
+          u.z &= 0x7fff7fffu;
+          u.w &= 0x7fff7fffu;
+          const ph16x8 fabs8 = *reinterpret_cast<const ph16x8*>(&u);  // |x~|
+          accS = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa[0][sk][lane], fx, accS, 0, 0, 0);
+          accT = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa[2][sk][lane], fabs8, accT, 0, 0, 0);
+          accS = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa[1][sk][lane], fx, accS, 0, 0, 0);
+        }
+      } else {
+#pragma unroll
+        for (int sk = 0; sk < KS; ++sk) {
+          const ph16x8 fx = xr[2 * sk + tb];
+          accS = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa[0][sk][lane], fx, accS, 0, 0, 0);
+          accS = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa[1][sk][lane], fx, accS, 0, 0, 0);
+        }
+      }
       const float xr_n = (tb == 0) == (hh == 0) ? xn : xo;  // |x~| of the tile row
-      const float c1 = eps * xr_n + abs_c, c2 = abs_c * xr_n;
+      const float c1 = eps_n * xr_n + abs_c, c2 = abs_c * xr_n;
       const bool huge = !(xr_n <= 0x1p100f);  // NaN, inf (fp16 overflow): exact chains
       uint32_t bt = 0u, am = 0u;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int j = (i & 3) + 8 * (i >> 2) + 4 * (int)hh;
         if (j < h) {
-          const float sv = tb ? accB[i] : accA[i];
-          const float bound = swn[j] * c1 + c2;
+          const float sv = accS[i], asv = __builtin_fabsf(sv);
+          const float bound = eps_t * accT[i] + (swn[j] * c1 + c2);  // (NaN, inf in T~: no call)
           bt |= (sv >= 0.0f ? 1u : 0u) << j;
-          am |= ((!(__builtin_fabsf(sv) > bound) || huge) ? 1u : 0u) << j;
+          am |= ((!(asv > bound) || !(asv <= 0x1.fffffep127f) || huge) ? 1u : 0u) << j;
         }
       }
-      bits[tb] = bt | (uint32_t)__shfl_xor((int)bt, 32, 64);
-      amb[tb] = am | (uint32_t)__shfl_xor((int)am, 32, 64);
+      bits[tb] = bt | xor32(bt);
+      amb[tb] = am | xor32(am);
     }
     const uint32_t row = g0 + lane;  // lane L writes tile A row L (L < 32) / tile B row L - 32
     const uint32_t mb = hh ? bits[1] : bits[0], ma = hh ? amb[1] : amb[0];
@@ -459,15 +510,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
         atomicAdd(&s_close, (uint32_t)__popc(ma));
         const uint32_t at = atomicAdd(&s_cnt, 1u);
         if (at < segcap) {
-          seg[at] = make_uint4(row, ma, key_bits, 0u);
+          seg[at] = make_uint4(row, ma, key_bits, slot);  // (the row is the lane's own: its slot)
           done = false;
         } else {
-          const float* x = X + (size_t)slots[row] * dp;
+          const float* x = X + (size_t)slot * dp;
           uint32_t a = ma;
           while (a) {
             const int j = __builtin_ctz(a);
             a &= a - 1u;
+            // (the row is re-read per hyperplane, 4 columns in flight: hoisted out of this loop
+            // it is D registers in the middle of the group, which spills; the path is a rare one)
+            asm volatile("" ::: "memory");
             float sd = 0.0f;  // -ffp-contract=off: the reference's mul, add order
+#pragma unroll 4
             for (int k = 0; k < D; ++k) sd = sd + swf[j * D + k] * x[k];
             if (sd >= 0.0f) key_bits |= 1u << j;
           }
@@ -478,18 +533,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     }
   };
   while (g0 < n) {
-    const uint32_t sl = slots[g0 + step + lane < n ? g0 + step + lane : 0u];  // the next group's
-    group(xr, g0);
+    const uint32_t nx = slots[g0 + step + lane < n ? g0 + step + lane : 0u];  // the next group's
+    group(xr, g0, sl);
     g0 += step;
     if (g0 >= n) break;
-    load_rows(xr, sl);
+    load_rows(xr, nx);
+    sl = nx;
   }
   __syncthreads();
-  // the close calls of this workgroup's rows
+  // the close calls of this workgroup's rows: the f32 row straight from the entry's slot
   const uint32_t cnt = min(s_cnt, segcap);
   for (uint32_t e = t; e < cnt; e += 256) {
     const uint4 f = seg[e];
-    const float* x = X + (size_t)slots[f.x] * dp;
+    const float* x = X + (size_t)f.w * dp;
     float4 u[D / 4];
 #pragma unroll
     for (int q = 0; q < D / 4; ++q) u[q] = *reinterpret_cast<const float4*>(x + 4 * q);
@@ -866,7 +922,7 @@ static void launch_h16(const Rows& r, const uint32_t* slots, uint32_t* keys, uin
   const uint32_t grid = std::min<uint32_t>((n + 255) / 256, gmax);
   uint32_t segcap = (pw.cap / 2) / grid;  // 16-B fix-up entries per workgroup
   if (pw.segcap) segcap = std::min(segcap, pw.segcap);  // "h16_segcap" (tests: the in-place path)
-  const float eps = h16_eps(r.d), abs_c = h16_abs(r.d);
+  const float eps = pw.h16_cs ? h16_eps(r.d) : h16_eps_t(r.d), abs_c = h16_abs(r.d);
   auto go = [&](auto screen) {
     screen<<<grid, 256, 0, s>>>(r.xh, r.x, r.dp, slots, keys, n, W, h, key_or, eps, abs_c, pw,
                                 segcap, kt, n_dev, woff_dev);
