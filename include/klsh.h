@@ -124,6 +124,16 @@ int klsh_abi_version(void);         /* KLSH_ABI_VERSION of the built library */
 int klsh_load_rows(klsh_ctx* ctx, const float* rows, uint64_t n, int d,
                    const uint64_t* member_offsets, const uint64_t* member_ids);
 
+/* The same load for rows that are in device memory already (an exception to "all pointers are
+ * host memory"): d_rows is memory of the context's device, n rows of d floats, row i starting
+ * i * row_stride floats in (row_stride >= d; a host pointer, another device's memory or a smaller
+ * stride: KLSH_E_ARG, and the previous load stays).  Every row is a singleton, {member_ids ?
+ * member_ids[i] : i}; member_ids is HOST memory.  Leaves exactly the state klsh_load_rows leaves
+ * for the same rows.  The caller's writes to d_rows must be complete before the call; d_rows is no
+ * longer read when it returns.  n = 0 is allowed. */
+int klsh_load_rows_device(klsh_ctx* ctx, const float* d_rows, uint64_t n, int d,
+                          uint64_t row_stride, const uint64_t* member_ids);
+
 /* Mode-C producer on the GPU (reference io/ioHT.cc:59-81 ReadHT + io/ioMatrix.cc:353-408
  * convertHTMat): counts is the whole sample-major kmer_count.bin image (d columns of n_total
  * uint16), the batch is rows [batch_offset, batch_offset+batch_size); v_kmers[j] =
@@ -235,6 +245,33 @@ int klsh_count(klsh_ctx* ctx, uint64_t* n_rows, uint64_t* n_members);
 /* Canonical order: rows (n_rows*d), member_offsets (n_rows+1), member_ids (n_members); any may
  * be NULL. */
 int klsh_result(klsh_ctx* ctx, float* rows, uint64_t* member_offsets, uint64_t* member_ids);
+
+/* The result on the device.  Its currency is the member NODE: the loaded members
+ * numbered 0 .. M-1 in load order (M: option "member_nodes"), whatever their ids —
+ *   after klsh_load_rows         node k is entry k of the loaded member_ids (row k when
+ *                                member_offsets is NULL),
+ *   after klsh_load_rows_device  node k is input row k,
+ *   after klsh_load_counts       node k is batch row k (the dropped rows included).
+ * Ids stay on the host: with `ids` the loaded member ids in node order, klsh_result's
+ * member_ids[m] equals ids[nodes[m]].
+ * klsh_result_device writes, into memory of the context's device (each may be NULL; a host
+ * pointer or another device's memory is KLSH_E_ARG): d_rows, the n_rows x d centroids, packed,
+ * in canonical order; d_member_offsets, n_rows + 1 entries, klsh_result's member_offsets;
+ * d_member_nodes, n_members entries, each row's members as nodes, in klsh_result's order;
+ * d_labels, M entries, labels[k] = the index in canonical order of the live row whose list holds
+ * node k, KLSH_NO_LABEL for a node no live row holds (a row klsh_load_counts dropped).  The lists
+ * are flattened by parallel list ranking in ceil(log2(longest list)) rounds (option
+ * "result_rounds" reads that count back); a broken member list is KLSH_E_STATE, as in
+ * klsh_result, never an endless walk.  Every output is complete when the call returns (the
+ * engine's stream is synchronized).  klsh_labels: the labels alone, copied to host memory.
+ * Options: "result_device" 1 = klsh_count takes n_members from, and klsh_result builds its
+ * offsets and ids with, the same kernels (the outputs are the same bytes; default 0);
+ * read-only "member_nodes", "result_rounds" and "result_rank_us" (the HIP-event time of those
+ * rounds in the last device result, microseconds). */
+#define KLSH_NO_LABEL 0xFFFFFFFFu
+int klsh_result_device(klsh_ctx* ctx, float* d_rows, uint32_t* d_member_offsets,
+                       uint32_t* d_member_nodes, uint32_t* d_labels);
+int klsh_labels(klsh_ctx* ctx, uint32_t* labels /* host, M entries */);
 
 /* ---- path functions, exposed for parity tests ------------------------------------------------- */
 /* Hash::LSH::random_projection(row, table) (reference hash/lshash.cc:44-59) for n rows on the

@@ -38,6 +38,7 @@ EXPORTED = (
     "klsh_check_reads", "klsh_extract_fastq", "klsh_build_khtable", "klsh_cuckoo_order",
     "klsh_kmc_info", "klsh_khtable_first", "klsh_bucket_runs", "klsh_row_state",
     "klsh_count_khtable", "klsh_kcount_listing", "klsh_count_kmc",
+    "klsh_load_rows_device", "klsh_result_device", "klsh_labels",
 )
 
 
@@ -191,6 +192,10 @@ def load_library() -> ctypes.CDLL:
         "klsh_version": (ctypes.c_char_p, []),
         "klsh_abi_version": (ctypes.c_int, []),
         "klsh_load_rows": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int, _P, _P]),
+        "klsh_load_rows_device": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int,
+                                                 ctypes.c_uint64, _P]),
+        "klsh_result_device": (ctypes.c_int, [_P, _P, _P, _P, _P]),
+        "klsh_labels": (ctypes.c_int, [_P, _P]),
         "klsh_load_counts": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64,
                                             ctypes.c_uint64, ctypes.c_int, _P]),
         "klsh_snapshot": (ctypes.c_int, [_P]),
@@ -265,6 +270,15 @@ def load_library() -> ctypes.CDLL:
 
 def _ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _torch_if_tensor(x):
+    """The torch module if x is a torch tensor, else None.  torch is never imported here: an
+    object can only be a tensor if its creator imported torch already."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    return torch if torch is not None and isinstance(x, torch.Tensor) else None
 
 
 def _check(rc: int, what: str) -> None:
@@ -441,6 +455,7 @@ class Engine:
         if not self._ctx:
             _check(err.value or -2, "klsh_create")
         self._lib = lib
+        self.device = device
         self.d = 0
 
     def close(self) -> None:
@@ -461,14 +476,48 @@ class Engine:
         self.close()
 
     # ---- loading
-    def load_rows(self, rows: np.ndarray, member_offsets: np.ndarray | None = None,
+    def load_rows(self, rows, member_offsets: np.ndarray | None = None,
                   member_ids: np.ndarray | None = None) -> None:
+        """Rows as a numpy array, or as a torch tensor (float32, 2-D, last-dimension stride 1, any
+        row stride >= d): one on this engine's GPU is read where it is (klsh_load_rows_device,
+        every row a singleton), a CPU tensor goes the numpy way, any other device raises."""
+        torch = _torch_if_tensor(rows)
+        if torch is not None:
+            if rows.device.type == "cpu":
+                rows = rows.detach().numpy()
+            else:
+                return self._load_rows_tensor(torch, rows, member_offsets, member_ids)
         rows = np.ascontiguousarray(rows, dtype=np.float32)
         n, d = rows.shape
         mo = None if member_offsets is None else np.ascontiguousarray(member_offsets, np.uint64)
         mi = None if member_ids is None else np.ascontiguousarray(member_ids, np.uint64)
         _check(self._lib.klsh_load_rows(self._ctx, _ptr(rows), n, d, _ptr(mo), _ptr(mi)),
                "klsh_load_rows")
+        self.d = d
+
+    def _torch_device(self, torch):
+        return torch.device("cuda", self.device)
+
+    def _load_rows_tensor(self, torch, rows, member_offsets, member_ids) -> None:
+        if rows.device != self._torch_device(torch):
+            raise KlshError(f"load_rows: the tensor is on {rows.device}, this engine on "
+                            f"{self._torch_device(torch)}")
+        if member_offsets is not None:
+            raise KlshError("load_rows: a device tensor is loaded as singleton rows "
+                            "(member_offsets must be None)")
+        if rows.dtype != torch.float32 or rows.dim() != 2:
+            raise KlshError("load_rows: the tensor must be float32 and 2-D")
+        n, d = rows.shape
+        if (d > 1 and rows.stride(1) != 1) or (n > 1 and rows.stride(0) < d):
+            raise KlshError("load_rows: the tensor needs last-dimension stride 1 and a row "
+                            f"stride >= d (strides {tuple(rows.stride())})")
+        stride = rows.stride(0) if n > 1 else d
+        mi = None if member_ids is None else np.ascontiguousarray(member_ids, np.uint64)
+        if mi is not None and mi.size != n:
+            raise KlshError("load_rows: one member id per row")
+        torch.cuda.current_stream(rows.device).synchronize()  # the caller's writes are complete
+        _check(self._lib.klsh_load_rows_device(self._ctx, ctypes.c_void_p(rows.data_ptr()), n, d,
+                                               stride, _ptr(mi)), "klsh_load_rows_device")
         self.d = d
 
     def load_counts(self, counts: np.ndarray, v_kmers: np.ndarray, batch_offset: int = 0,
@@ -642,6 +691,38 @@ class Engine:
         _check(self._lib.klsh_result(self._ctx, _ptr(rows), _ptr(off), _ptr(ids)),
                "klsh_result")
         return rows, off, ids
+
+    def result_device(self):
+        """The result left on this engine's GPU, as torch tensors (``klsh_result_device``):
+        (rows (n, d) float32, member_offsets (n+1,) uint32, member_nodes (m,) uint32, labels (M,)
+        uint32).  Nodes number the loaded members in load order; labels[k] is the row of node k,
+        0xFFFFFFFF for a node no live row holds (include/klsh.h)."""
+        import torch
+
+        dev = self._torch_device(torch)
+        n = ctypes.c_uint64(0)
+        _check(self._lib.klsh_count(self._ctx, ctypes.byref(n), None), "klsh_count")
+        n, big_m = n.value, self.get_option("member_nodes")
+        rows = torch.empty((n, self.d), dtype=torch.float32, device=dev)
+        off = torch.empty(n + 1, dtype=torch.uint32, device=dev)
+        nodes = torch.empty(big_m, dtype=torch.uint32, device=dev)  # (the live members: <= M)
+        labels = torch.empty(big_m, dtype=torch.uint32, device=dev)
+        # the engine writes on its own stream: nothing queued on torch's may still use this memory
+        torch.cuda.current_stream(dev).synchronize()
+
+        def p(t):
+            return ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+
+        _check(self._lib.klsh_result_device(self._ctx, p(rows), p(off), p(nodes), p(labels)),
+               "klsh_result_device")
+        return rows, off, nodes[: int(off[-1].item())], labels
+
+    def labels(self) -> np.ndarray:
+        """labels[k] = the result row whose member list holds node k (``klsh_labels``), uint32,
+        0xFFFFFFFF for a node no live row holds."""
+        out = np.zeros(self.get_option("member_nodes"), dtype=np.uint32)
+        _check(self._lib.klsh_labels(self._ctx, _ptr(out)), "klsh_labels")
+        return out
 
     def row_state(self) -> dict:
         """The cached per-slot state of the live rows, in result() order (``klsh_row_state``):

@@ -392,6 +392,46 @@ void launch_shadow_build(const Rows& r, uint64_t n, hipStream_t s);
 void launch_gather_rows(const Rows& r, const uint32_t* order, uint32_t n, float* out,
                         hipStream_t s);
 
+// ---- the result on the device (klsh_result.hip) -------------------------------
+// Every launch strides over its range on its own and takes option "grid_cap" (cap_grid).
+constexpr uint32_t kResItems = 8;                  // live rows per lane of an offsets tile
+constexpr uint32_t kResTile = 256 * kResItems;     // live rows per offsets tile
+inline uint32_t result_tiles(uint64_t n) { return (uint32_t)((n + kResTile - 1) / kResTile); }
+// hdr: kResHdrWords words, zeroed by the caller before the first launch of a result
+constexpr uint32_t kResTotal = 0;     // members of the live rows (= off[n])
+constexpr uint32_t kResMaxCnt = 1;    // the longest live member list
+constexpr uint32_t kResLabelled = 2;  // nodes that found a live row (k_rank_emit)
+constexpr uint32_t kResErr = 3;       // kResErr* bits
+constexpr uint32_t kResHdrWords = 8;
+constexpr uint32_t kResErrOrder = 1u;  // a live slot outside the table
+constexpr uint32_t kResErrList = 2u;   // a link or tail outside the table, a node past its row's cnt
+// off[i] = sum of cnt[order[j]] over j < i, off[n] = hdr[kResTotal] = the total, hdr[kResMaxCnt] =
+// the largest; three launches (tile sums, one workgroup over the sums, apply).  tsum, tmax:
+// result_tiles(n) words each.
+void launch_result_offsets(const uint32_t* order, const uint32_t* cnt, uint32_t n, uint32_t slots,
+                           uint32_t* tsum, uint32_t* tmax, uint32_t* off, uint32_t* hdr,
+                           hipStream_t s, uint32_t grid_cap = 0);
+// rowof[0..members) = KLSH_NO_LABEL, then rowof[tail[order[i]]] = i for the live rows with members
+void launch_result_rowof(const uint32_t* order, const uint32_t* cnt, const uint32_t* tail,
+                         uint32_t n, uint32_t slots, uint32_t members, uint32_t* rowof,
+                         uint32_t* hdr, hipStream_t s, uint32_t grid_cap = 0);
+// List ranking of the member chains by `rounds` >= ceil(log2(longest chain)) rounds of pointer
+// jumping over the packed (jmp | dist << 32) words, st0 and st1 in turn (members words each).
+// Returns the buffer with the result: jmp = the node's chain end, dist = its links to it.
+// after_init (may be null): recorded between the init launch and the first round.
+const uint64_t* launch_list_rank(const uint32_t* nxt, uint32_t members, uint32_t rounds,
+                                 uint64_t* st0, uint64_t* st1, uint32_t* hdr, hipStream_t s,
+                                 uint32_t grid_cap = 0, hipEvent_t after_init = nullptr);
+// labels[v] = i = rowof[jmp of v]; nodes[off[i] + cnt[order[i]] - 1 - dist] = v where i is a row
+// (labels, nodes: either may be null); hdr[kResLabelled] += such nodes
+void launch_result_emit(const uint64_t* st, const uint32_t* rowof, const uint32_t* order,
+                        const uint32_t* cnt, const uint32_t* off, uint32_t members, uint32_t n,
+                        uint32_t slots, uint32_t* labels, uint32_t* nodes, uint32_t* hdr,
+                        hipStream_t s, uint32_t grid_cap = 0);
+// cnt = 1, head = tail = order = i, nxt = kNil for i < n (rows loaded as singletons)
+void launch_init_singletons(const Rows& r, uint32_t* order, uint32_t n, hipStream_t s,
+                            uint32_t grid_cap = 0);
+
 // Floating-point self test: sqrt_out[i] = sqrtf(a[i]); div_out[i] = a[i] / b[i] as the merge
 // kernels evaluate them.
 void launch_fp_selftest(const float* a, const float* b, uint32_t n, float* sqrt_out,
