@@ -19,23 +19,13 @@
 #include <string.h>
 #include <zlib.h>
 
-#include <chrono>
 #include <cmath>
 #include <string>
 #include <vector>
 
-#include "klsh.h"
-#include "klsh_internal.h"
+#include "klsh_ctx.h"
 
 namespace {
-
-using klsh::set_error;
-
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(
-             std::chrono::steady_clock::now().time_since_epoch())
-      .count();
-}
 
 // ============================================ ALGLIB 3.15.0 restated (Cephes algorithms) ======
 // Constants of utils/alglib-3.15.0/src/ap.h:1008-1011.
@@ -532,13 +522,6 @@ struct klsh_kset {
   uint64_t n = 0;
 };
 
-#define KLSH_XHIP(call)                                                          \
-  do {                                                                           \
-    hipError_t e_ = (call);                                                      \
-    if (e_ != hipSuccess)                                                        \
-      return set_error(KLSH_E_HIP, (std::string(#call) + " -> " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
 extern "C" {
 
 int klsh_ttest2(const double* x, int64_t n, const double* y, int64_t m, double* bothtails,
@@ -610,8 +593,8 @@ klsh_kset* klsh_kset_create(klsh_ctx* ctx, const uint64_t* kmers, uint64_t n, in
     return nullptr;
   };
   if (!ctx || (n && !kmers)) return bad(set_error(KLSH_E_ARG, "null argument"));
-  if (hipSetDevice(klsh::ctx_device(ctx)) != hipSuccess) return bad(set_error(KLSH_E_HIP, "hipSetDevice"));
-  const hipStream_t s = klsh::ctx_stream(ctx);
+  if (hipSetDevice(ctx->device) != hipSuccess) return bad(set_error(KLSH_E_HIP, "hipSetDevice"));
+  const hipStream_t s = ctx->stream;
   uint64_t cap = 1024;
   while (cap < 2 * n) cap <<= 1;  // load factor <= 1/2
   klsh_kset* ks = new klsh_kset();
@@ -624,7 +607,7 @@ klsh_kset* klsh_kset_create(klsh_ctx* ctx, const uint64_t* kmers, uint64_t n, in
   ok = ok && hipMemsetAsync(ks->tab, 0xFF, cap * 8, s) == hipSuccess;
   ok = ok && (n == 0 || hipMemcpyAsync(dk, kmers, n * 8, hipMemcpyHostToDevice, s) == hipSuccess);
   if (ok) {
-    klsh::launch_kset_insert(dk, n, ks->tab, ks->mask, s, klsh::ctx_grid_cap(ctx));
+    klsh::launch_kset_insert(dk, n, ks->tab, ks->mask, s, ctx->mw.grid_cap);
     ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
   }
   if (dk) (void)hipFree(dk);
@@ -639,7 +622,7 @@ klsh_kset* klsh_kset_create(klsh_ctx* ctx, const uint64_t* kmers, uint64_t n, in
 
 void klsh_kset_destroy(klsh_kset* ks) {
   if (!ks) return;
-  (void)hipSetDevice(klsh::ctx_device(ks->ctx));
+  (void)hipSetDevice(ks->ctx->device);
   if (ks->tab) (void)hipFree(ks->tab);
   delete ks;
 }
@@ -651,8 +634,8 @@ int klsh_check_reads(klsh_ctx* ctx, const klsh_kset* ks, const char* seq,
     return set_error(KLSH_E_ARG, "bad argument");
   if (k < 1 || k > 32) return set_error(KLSH_E_RANGE, "k must be in [1, 32] (Kmer::MAX_K)");
   if (n_reads == 0) return KLSH_OK;
-  KLSH_XHIP(hipSetDevice(klsh::ctx_device(ctx)));
-  const hipStream_t s = klsh::ctx_stream(ctx);
+  KLSH_HIP(hipSetDevice(ctx->device));
+  const hipStream_t s = ctx->stream;
   const uint64_t nb = read_offsets[n_reads] - read_offsets[0];
   std::vector<uint64_t> off(read_offsets, read_offsets + n_reads + 1);
   for (auto& o : off) o -= read_offsets[0];
@@ -667,7 +650,7 @@ int klsh_check_reads(klsh_ctx* ctx, const klsh_kset* ks, const char* seq,
        hipMemcpyAsync(doff, off.data(), off.size() * 8, hipMemcpyHostToDevice, s) == hipSuccess;
   if (ok) {
     klsh::launch_check_reads(dseq, doff, n_reads, k, kmer_vote, ks->tab, ks->mask, dhit, dflag, s,
-                             klsh::ctx_grid_cap(ctx));
+                             ctx->mw.grid_cap);
     ok = hipGetLastError() == hipSuccess;
   }
   ok = ok && (!hits || hipMemcpyAsync(hits, dhit, n_reads * 4, hipMemcpyDeviceToHost, s) == hipSuccess) &&
@@ -691,8 +674,8 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
     return set_error(KLSH_E_ARG, "klsh_extract_stats.struct_size != sizeof: built against another klsh.h");
   klsh_extract_stats local{};
   local.struct_size = sizeof(local);
-  KLSH_XHIP(hipSetDevice(klsh::ctx_device(ctx)));
-  const hipStream_t s = klsh::ctx_stream(ctx);
+  KLSH_HIP(hipSetDevice(ctx->device));
+  const hipStream_t s = ctx->stream;
   FastqReader rdr;
   if (!rdr.open(in_path)) return set_error(KLSH_E_ARG, (std::string("cannot open ") + in_path).c_str());
   FILE* of = fopen(out_path, "wb");
@@ -750,29 +733,29 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
       if (sl.dseq) (void)hipFree(sl.dseq);
       sl.dseq = nullptr;
       sl.cap_b = nb + 64 > kBases + (64u << 10) ? nb + 64 : kBases + (64u << 10);
-      KLSH_XHIP(hipMalloc((void**)&sl.dseq, sl.cap_b));
+      KLSH_HIP(hipMalloc((void**)&sl.dseq, sl.cap_b));
     }
-    if (nb) KLSH_XHIP(hipMemcpyAsync(sl.dseq, b.seq.data(), nb, hipMemcpyHostToDevice, s));
-    KLSH_XHIP(hipMemcpyAsync(sl.doff, b.seq_off.data(), (sl.n + 1) * 8, hipMemcpyHostToDevice, s));
-    KLSH_XHIP(hipEventRecord(sl.e0, s));
+    if (nb) KLSH_HIP(hipMemcpyAsync(sl.dseq, b.seq.data(), nb, hipMemcpyHostToDevice, s));
+    KLSH_HIP(hipMemcpyAsync(sl.doff, b.seq_off.data(), (sl.n + 1) * 8, hipMemcpyHostToDevice, s));
+    KLSH_HIP(hipEventRecord(sl.e0, s));
     klsh::launch_check_reads(sl.dseq, sl.doff, sl.n, k, kmer_vote, ks->tab, ks->mask, sl.dhit,
-                             sl.dflag, s, klsh::ctx_grid_cap(ctx));
-    KLSH_XHIP(hipGetLastError());
-    KLSH_XHIP(hipEventRecord(sl.e1, s));
-    KLSH_XHIP(hipMemcpyAsync(sl.hflag, sl.dflag, sl.n, hipMemcpyDeviceToHost, s));
-    KLSH_XHIP(hipEventRecord(sl.done, s));
+                             sl.dflag, s, ctx->mw.grid_cap);
+    KLSH_HIP(hipGetLastError());
+    KLSH_HIP(hipEventRecord(sl.e1, s));
+    KLSH_HIP(hipMemcpyAsync(sl.hflag, sl.dflag, sl.n, hipMemcpyDeviceToHost, s));
+    KLSH_HIP(hipEventRecord(sl.done, s));
     return KLSH_OK;
   };
   auto finish = [&](int si) -> int {
     Slot& sl = slot[si];
     FastqReader& b = keep[si];
-    KLSH_XHIP(hipEventSynchronize(sl.e1));
+    KLSH_HIP(hipEventSynchronize(sl.e1));
     float ms = 0.0f;
     (void)hipEventElapsedTime(&ms, sl.e0, sl.e1);
     local.kernel_ms += ms;
     // the flag copy behind this batch's kernel — not the stream, which by now also holds the next
     // batch: waiting for that would serialise the host parse behind every kernel
-    KLSH_XHIP(hipEventSynchronize(sl.done));
+    KLSH_HIP(hipEventSynchronize(sl.done));
     out.clear();
     for (uint64_t i = 0; i < sl.n; ++i) {
       const uint64_t len = b.seq_off[i + 1] - b.seq_off[i];

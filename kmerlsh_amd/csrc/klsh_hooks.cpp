@@ -1,0 +1,321 @@
+// Test hooks behind the C ABI (include/klsh.h): single steps of the loop on caller data, and the
+// per-slot state the result does not show.
+#include <string.h>
+
+#include <algorithm>
+#include <array>
+
+#include "klsh_loop.h"
+
+using klsh::Counters;
+using klsh::Rows;
+
+extern "C" {
+
+// The per-slot state klsh_result does not show, for the live rows in its order: plain copies of
+// the device arrays and a host gather (read-only; on a context of a comm group, this rank's
+// replica).
+int klsh_row_state(klsh_ctx* ctx, float* nrm, uint32_t* cnt, uint16_t* image,
+                   uint64_t* pad_nonzero, uint64_t* bad_links) {
+  if (!ctx) return fail(KLSH_E_ARG, "null ctx");
+  if (!ctx->loaded) return fail(KLSH_E_STATE, "nothing loaded");
+  KLSH_HIP(hipSetDevice(ctx->device));
+  KLSH_HIP(hipStreamSynchronize(ctx->stream));  // (a load's image build may still be in flight)
+  const uint64_t n = ctx->n_live, S = ctx->slots, M = ctx->members;
+  const int d = ctx->d, dp = ctx->dp;
+  std::vector<uint32_t> ord(n);
+  if (n) KLSH_HIP(hipMemcpy(ord.data(), ctx->order, 4 * n, hipMemcpyDeviceToHost));
+  for (uint32_t sl : ord)
+    if (sl >= S) return fail(KLSH_E_STATE, "corrupt live order");
+  if (nrm && n) {
+    std::vector<float> a(S);
+    KLSH_HIP(hipMemcpy(a.data(), ctx->rows.nrm, 4 * S, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; ++i) nrm[i] = a[ord[i]];
+  }
+  std::vector<uint32_t> c(S);
+  if (S) KLSH_HIP(hipMemcpy(c.data(), ctx->rows.cnt, 4 * S, hipMemcpyDeviceToHost));
+  if (cnt)
+    for (uint64_t i = 0; i < n; ++i) cnt[i] = c[ord[i]];
+  if (image && n && ctx->rows.xh) {
+    std::vector<uint16_t> a(S * (uint64_t)dp);
+    KLSH_HIP(hipMemcpy(a.data(), ctx->rows.xh, 2 * a.size(), hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; ++i)
+      memcpy(image + i * d, a.data() + (uint64_t)ord[i] * dp, 2 * (size_t)d);
+  }
+  if (pad_nonzero) {
+    uint64_t bad = 0;
+    if (n && dp > d) {
+      std::vector<uint32_t> a(S * (uint64_t)dp);
+      KLSH_HIP(hipMemcpy(a.data(), ctx->rows.x, 4 * a.size(), hipMemcpyDeviceToHost));
+      for (uint64_t i = 0; i < n; ++i)
+        for (int k = d; k < dp; ++k) bad += a[(uint64_t)ord[i] * dp + k] != 0u;
+    }
+    *pad_nonzero = bad;
+  }
+  if (bad_links) {
+    std::vector<uint32_t> head(S), tail(S), nxt(M);
+    if (S) {
+      KLSH_HIP(hipMemcpy(head.data(), ctx->rows.head, 4 * S, hipMemcpyDeviceToHost));
+      KLSH_HIP(hipMemcpy(tail.data(), ctx->rows.tail, 4 * S, hipMemcpyDeviceToHost));
+    }
+    if (M) KLSH_HIP(hipMemcpy(nxt.data(), ctx->rows.nxt, 4 * M, hipMemcpyDeviceToHost));
+    uint64_t bad = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+      // exactly cnt nodes from head, the last of them tail (an empty list: head == tail == nil)
+      const uint32_t want = c[ord[i]];
+      uint32_t node = head[ord[i]], last = klsh::kNil, len = 0;
+      while (node != klsh::kNil && node < M && len <= want) {
+        last = node;
+        node = nxt[node];
+        ++len;
+      }
+      bad += !(node == klsh::kNil && len == want && last == tail[ord[i]]);
+    }
+    *bad_links = bad;
+  }
+  return 0;
+}
+
+// The projection kernels the loop uses, on caller rows: the same dispatch (launch_project) with
+// the context's projection options, the fp16 row image built from the rows where the loop keeps
+// one (d = 16, 32, 64), so the certified screens and their exact fix-up paths are what a test of
+// this entry point exercises.
+int klsh_hash_keys(klsh_ctx* ctx, const float* rows, uint64_t n, int d, const float* table, int h,
+                   uint32_t* keys) {
+  if (!ctx || (!rows && n) || (!keys && n) || (!table && h > 0)) return fail(KLSH_E_ARG, "null argument");
+  if (d <= 0 || d > 4096 || h < 0 || h > 31) return fail(KLSH_E_RANGE, "d or h out of range");
+  if (n >= 0xFFFFFFF0ull) return fail(KLSH_E_RANGE, "rows >= 2^32");
+  ctx->last_hash_kernel = klsh::kPkNone;
+  ctx->last_hash_close = 0;
+  if (n == 0) return 0;
+  KLSH_HIP(hipSetDevice(ctx->device));
+  const int dp = (d + 3) & ~3;
+  Rows r{};
+  r.d = d;
+  r.dp = dp;
+  uint32_t *slots = nullptr, *dkeys = nullptr;
+  float* W = nullptr;
+  uint16_t* xh = nullptr;
+  klsh::ProjectWork pw = ctx->pw;  // the context's launch options, fresh workspaces
+  pw.fix = nullptr;
+  pw.ws = nullptr;
+  auto release = [&] {
+    dfree(r.x); dfree(slots); dfree(dkeys); dfree(W); dfree(pw.fix); dfree(pw.ws); dfree(xh);
+  };
+  int e = 0;
+  const bool image = ctx->shadow_wanted(d);
+  if ((e = dalloc(&r.x, n * dp)) || (e = dalloc(&slots, n)) || (e = dalloc(&dkeys, n)) ||
+      (e = dalloc(&W, (uint64_t)std::max(h, 1) * dp)) || (e = dalloc(&pw.fix, n)) ||
+      (e = dalloc(&pw.ws, 64)) || (image && (e = dalloc(&xh, n * dp)))) {
+    release();
+    return e;
+  }
+  pw.cap = (uint32_t)n;
+  r.xh = xh;
+  hipStream_t s = ctx->stream;
+  std::vector<uint32_t> iota(n);
+  for (uint64_t i = 0; i < n; ++i) iota[i] = (uint32_t)i;
+  int rc = 0;
+  if (hipMemsetAsync(r.x, 0, sizeof(float) * n * dp, s) != hipSuccess ||
+      hipMemcpy2DAsync(r.x, 4 * dp, rows, 4 * d, 4 * d, n, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemsetAsync(W, 0, sizeof(float) * std::max(h, 1) * dp, s) != hipSuccess ||
+      hipMemsetAsync(pw.ws, 0, sizeof(uint32_t) * 64, s) != hipSuccess ||
+      (h > 0 && hipMemcpy2DAsync(W, 4 * dp, table, 4 * d, 4 * d, h, hipMemcpyHostToDevice, s) !=
+                    hipSuccess) ||
+      hipMemcpyAsync(slots, iota.data(), 4 * n, hipMemcpyHostToDevice, s) != hipSuccess) {
+    rc = fail(KLSH_E_HIP, "upload");
+  } else {
+    if (image) klsh::launch_shadow_build(r, n, s);
+    const int kern = klsh::launch_project(r, slots, dkeys, (uint32_t)n, W, h, 0u, s, &pw);
+    uint32_t w[64];
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(keys, dkeys, 4 * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(w, pw.ws, sizeof(w), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+      rc = fail(KLSH_E_HIP, "projection");
+    } else {
+      ctx->last_hash_kernel = kern;
+      ctx->last_hash_close = klsh::proj_close_pairs(w);
+    }
+  }
+  (void)hipStreamSynchronize(s);
+  release();
+  return rc;
+}
+
+int klsh_bucket_sort(klsh_ctx* ctx, const uint32_t* keys, uint64_t n, int bits,
+                     uint32_t* sorted_keys, uint32_t* perm) {
+  if (!ctx || (n && (!keys || !sorted_keys || !perm))) return fail(KLSH_E_ARG, "null argument");
+  if (bits < 0 || bits > 32) return fail(KLSH_E_RANGE, "bits out of range");
+  if (n >= 0xFFFFFFF0ull) return fail(KLSH_E_RANGE, "keys >= 2^32");
+  if (n == 0) return 0;
+  KLSH_HIP(hipSetDevice(ctx->device));
+  uint32_t *k0 = nullptr, *v0 = nullptr, *k1 = nullptr, *v1 = nullptr, *ws = nullptr, *ts = nullptr;
+  Counters* ctr = nullptr;
+  const uint64_t ts_words = klsh::scan_ws_words(n);
+  int e = 0;
+  auto release = [&] {
+    dfree(k0); dfree(v0); dfree(k1); dfree(v1); dfree(ws); dfree(ts); dfree(ctr);
+  };
+  if ((e = dalloc(&k0, n)) || (e = dalloc(&v0, n)) || (e = dalloc(&k1, n)) || (e = dalloc(&v1, n)) ||
+      (e = dalloc(&ws, klsh::sort_ws_words(n))) || (e = dalloc(&ts, ts_words)) ||
+      (e = dalloc(&ctr, 1))) {
+    release();
+    return e;
+  }
+  hipStream_t s = ctx->stream;
+  std::vector<uint32_t> iota(n);
+  for (uint64_t i = 0; i < n; ++i) iota[i] = (uint32_t)i;
+  Counters hc{};
+  int rc = 0;
+  uint32_t *ok = nullptr, *ov = nullptr;
+  if (hipMemsetAsync(ws, 0, sizeof(uint32_t) * klsh::sort_ws_words(n), s) != hipSuccess ||
+      hipMemsetAsync(ts, 0, sizeof(uint32_t) * ts_words, s) != hipSuccess ||
+      hipMemsetAsync(ctr, 0, sizeof(Counters), s) != hipSuccess ||
+      hipMemcpyAsync(k0, keys, 4 * n, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(v0, iota.data(), 4 * n, hipMemcpyHostToDevice, s) != hipSuccess) {
+    rc = fail(KLSH_E_HIP, "upload");
+  } else {
+    klsh::radix_sort(k0, v0, k1, v1, (uint32_t)n, bits, ws, &ok, &ov, s);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(sorted_keys, ok, 4 * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(perm, ov, 4 * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(&hc, ctr, sizeof(Counters), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      rc = fail(KLSH_E_HIP, "sort");
+    else if (hc.err)
+      rc = fail(KLSH_E_HIP, "device protocol failure in the sort");
+  }
+  (void)hipStreamSynchronize(s);
+  release();
+  return rc;
+}
+
+// The run finding of merge_main alone on caller keys (a test hook): every run of 2+ equal keys
+// of n sorted keys with its list, in start order.
+int klsh_bucket_runs(klsh_ctx* ctx, const uint32_t* sorted_keys, uint64_t n, int bucket_thr,
+                     uint64_t* n_runs, uint32_t* starts, uint32_t* lengths, int32_t* lists) {
+  if (!ctx || !n_runs || (n && !sorted_keys)) return fail(KLSH_E_ARG, "null argument");
+  if (n >= 0xFFFFFFF0ull) return fail(KLSH_E_RANGE, "keys >= 2^32");
+  const uint64_t cap = *n_runs;
+  *n_runs = 0;
+  if (n == 0) return 0;
+  KLSH_HIP(hipSetDevice(ctx->device));
+  using klsh::kBigClasses;
+  using klsh::kGroupClasses;
+  klsh::MergeWork w{};
+  uint32_t* dk = nullptr;
+  klsh::RunCounters* rc = nullptr;
+  auto release = [&] {
+    dfree(dk); dfree(rc); dfree(w.run_ws); dfree(w.huge); dfree(w.over);
+    for (auto& c : w.cls) dfree(c);
+    for (auto& c : w.big) dfree(c);
+  };
+  int e = 0;
+  if ((e = dalloc(&dk, n)) || (e = dalloc(&rc, 1)) || (e = dalloc(&w.run_ws, klsh::run_ws_words(n))) ||
+      (e = dalloc(&w.huge, n / 897 + 64)) || (e = dalloc(&w.over, n / 2 + 64))) {
+    release();
+    return e;
+  }
+  for (int c = 0; c < kGroupClasses && !e; ++c) e = dalloc(&w.cls[c], klsh::group_class_capacity(c, n));
+  for (int c = 0; c < kBigClasses && !e; ++c)
+    e = dalloc(&w.big[c], n / ((c ? klsh::kBigRows[c - 1] : 64) + 1) + 64);
+  if (e) {
+    release();
+    return e;
+  }
+  w.rc = rc;
+  w.kt = klsh::kNoTime;
+  hipStream_t s = ctx->stream;
+  klsh::RunCounters hc{};
+  int rc_ = 0;
+  if (hipMemsetAsync(rc, 0, sizeof(*rc), s) != hipSuccess ||
+      hipMemcpyAsync(dk, sorted_keys, 4 * n, hipMemcpyHostToDevice, s) != hipSuccess) {
+    rc_ = fail(KLSH_E_HIP, "upload");
+  } else {
+    klsh::launch_runs(dk, 0, (uint32_t)n, bucket_thr, w, s);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(&hc, rc, sizeof(hc), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      rc_ = fail(KLSH_E_HIP, "run finding");
+  }
+  std::vector<std::array<uint32_t, 3>> runs;  // (start, length, list)
+  auto take = [&](const uint2* list, uint32_t count, int l) -> int {
+    std::vector<uint2> h(count);
+    if (count && hipMemcpy(h.data(), list, sizeof(uint2) * count, hipMemcpyDeviceToHost) != hipSuccess)
+      return fail(KLSH_E_HIP, "list copy");
+    for (const uint2& x : h) runs.push_back({x.x, x.y, (uint32_t)l});
+    return 0;
+  };
+  for (int c = 0; c < kGroupClasses && !rc_; ++c) rc_ = take(w.cls[c], hc.n_cls[c].v, c);
+  for (int c = 0; c < kBigClasses && !rc_; ++c) rc_ = take(w.big[c], hc.n_big[c].v, kGroupClasses + c);
+  if (!rc_) rc_ = take(w.huge, hc.n_huge.v, klsh::kRunListCount - 2);
+  if (!rc_) rc_ = take(w.over, hc.n_over.v, klsh::kRunListCount - 1);
+  release();
+  if (rc_) return rc_;
+  std::sort(runs.begin(), runs.end());
+  *n_runs = runs.size();
+  if (runs.size() > cap) return fail(KLSH_E_RANGE, "more runs than the output holds (see *n_runs)");
+  for (size_t i = 0; i < runs.size(); ++i) {
+    if (starts) starts[i] = runs[i][0];
+    if (lengths) lengths[i] = runs[i][1];
+    if (lists) lists[i] = (int32_t)runs[i][2];
+  }
+  return 0;
+}
+
+int klsh_pcluster(klsh_ctx* ctx, float thr) {
+  if (!ctx) return fail(KLSH_E_ARG, "null ctx");
+  if (!ctx->loaded) return fail(KLSH_E_STATE, "nothing loaded");
+  KLSH_HIP(hipSetDevice(ctx->device));
+  const uint32_t n = (uint32_t)ctx->n_live;
+  if (n == 0) return 0;
+  hipStream_t s = ctx->stream;
+  if (int e = ctx->reset_counters()) return e;
+  ctx->mw.huge_fold = ctx->huge_fold_always ? 1u : 0u;
+  ctx->mw.huge_cap = 0;
+  KLSH_HIP(hipMemsetAsync(ctx->keys, 0, 4ull * n, s));  // one bucket: every key equal
+  uint64_t dummy = 0;
+  if (int e = klsh::merge_and_compact(ctx, ctx->keys, ctx->order, n, thr, -1, 0, &dummy, nullptr,
+                                      false))
+    return e;
+  KLSH_HIP(hipStreamSynchronize(s));  // see klsh_cluster: the order may still be in flight
+  return 0;
+}
+
+int klsh_hyperplanes(uint32_t seed_base, uint64_t* rng_counter, int h, int d, float* table) {
+  if (!rng_counter || (!table && h > 0) || d <= 0 || h < 0) return fail(KLSH_E_ARG, "bad argument");
+  klsh_host_hyperplanes(seed_base, *rng_counter, (uint64_t)h, d, d, table, 1);
+  *rng_counter += (uint64_t)h;
+  return 0;
+}
+
+int klsh_fp_selftest(klsh_ctx* ctx, const float* a, const float* b, uint64_t n, float* sqrt_out,
+                     float* div_out) {
+  if (!ctx || !a || !b || !sqrt_out || !div_out) return fail(KLSH_E_ARG, "null argument");
+  if (n == 0) return 0;
+  KLSH_HIP(hipSetDevice(ctx->device));
+  float *da = nullptr, *db = nullptr, *ds = nullptr, *dd = nullptr;
+  int e = 0;
+  if ((e = dalloc(&da, n)) || (e = dalloc(&db, n)) || (e = dalloc(&ds, n)) || (e = dalloc(&dd, n))) {
+    dfree(da); dfree(db); dfree(ds); dfree(dd);
+    return e;
+  }
+  hipStream_t s = ctx->stream;
+  int rc = 0;
+  if (hipMemcpyAsync(da, a, 4 * n, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(db, b, 4 * n, hipMemcpyHostToDevice, s) != hipSuccess) {
+    rc = fail(KLSH_E_HIP, "upload");
+  } else {
+    klsh::launch_fp_selftest(da, db, (uint32_t)n, ds, dd, s);
+    if (hipMemcpyAsync(sqrt_out, ds, 4 * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(div_out, dd, 4 * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      rc = fail(KLSH_E_HIP, "selftest");
+  }
+  (void)hipStreamSynchronize(s);
+  dfree(da); dfree(db); dfree(ds); dfree(dd);
+  return rc;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
-// Internal interface between the host engine (klsh_engine.cpp) and the gfx950 kernels
-// (klsh_kernels.hip).  Not part of the C ABI.
+// Internal interface between the host units (the .cpp files; their shared context is klsh_ctx.h,
+// which the kernels never see) and the gfx950 kernels (the .hip files).  Not part of the C ABI.
 #pragma once
 
 #include <hip/hip_ext.h>
@@ -604,14 +604,5 @@ struct KcountHooks {
   std::vector<std::vector<uint64_t>> values;  // per sample: the listed KMC values, ascending
   std::vector<std::vector<uint32_t>> counts;
 };
-
-// The engine's context, for the other host translation units (klsh_extract.cpp, klsh_kmc.cpp,
-// klsh_kcount.cpp).
-int ctx_device(const klsh_ctx* ctx);
-hipStream_t ctx_stream(const klsh_ctx* ctx);
-KmcHooks& ctx_kmc(klsh_ctx* ctx);
-KcountHooks& ctx_kcount(klsh_ctx* ctx);
-uint32_t ctx_grid_cap(const klsh_ctx* ctx);  // option "grid_cap" (mode E's launches)
-int set_error(int code, const char* msg);  // sets klsh_last_error(), returns code
 
 }  // namespace klsh

@@ -20,30 +20,13 @@
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <string>
 #include <vector>
 
-#include "klsh.h"
-#include "klsh_internal.h"
+#include "klsh_ctx.h"
 
 namespace {
-
-using klsh::set_error;
-
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(
-             std::chrono::steady_clock::now().time_since_epoch())
-      .count();
-}
-
-#define KLSH_CRET(call)                                                                   \
-  do {                                                                                    \
-    hipError_t e_ = (call);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return set_error(KLSH_E_HIP, (std::string(#call) + " -> " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
 
 constexpr uint64_t kBatchReads = 1ull << 18, kTableSlots = 1ull << 22;
 
@@ -101,7 +84,7 @@ int db_prefix_length(int k, uint64_t n) {
 class DbWriter {
  public:
   DbWriter(klsh_ctx* ctx, int k, uint32_t count_min, klsh_kmcdb_stats& st)
-      : hooks_(klsh::ctx_kcount(ctx)), s_(klsh::ctx_stream(ctx)), k_(k), count_min_(count_min),
+      : hooks_(ctx->kcount), s_(ctx->stream), k_(k), count_min_(count_min),
         st_(st) {}
   ~DbWriter() {
     (void)hipStreamSynchronize(s_);  // no copy into the pinned buffers stays queued
@@ -114,9 +97,9 @@ class DbWriter {
   }
   int init() {
     for (auto& b : buf_) {
-      KLSH_CRET(hipEventCreate(&b.e0));
-      KLSH_CRET(hipEventCreate(&b.e1));
-      KLSH_CRET(hipEventCreate(&b.done));
+      KLSH_HIP(hipEventCreate(&b.e0));
+      KLSH_HIP(hipEventCreate(&b.e1));
+      KLSH_HIP(hipEventCreate(&b.done));
     }
     return KLSH_OK;
   }
@@ -167,7 +150,7 @@ class DbWriter {
 
   int reserve(uint64_t bytes) {
     if (bytes <= cap_) return KLSH_OK;
-    KLSH_CRET(hipStreamSynchronize(s_));
+    KLSH_HIP(hipStreamSynchronize(s_));
     if (dev_) (void)hipFree(dev_);
     dev_ = nullptr;
     cap_ = 0;
@@ -175,8 +158,8 @@ class DbWriter {
       if (b.host) (void)hipHostFree(b.host);
       b.host = nullptr;
     }
-    KLSH_CRET(hipMalloc((void**)&dev_, bytes));
-    for (auto& b : buf_) KLSH_CRET(hipHostMalloc((void**)&b.host, bytes, hipHostMallocDefault));
+    KLSH_HIP(hipMalloc((void**)&dev_, bytes));
+    for (auto& b : buf_) KLSH_HIP(hipHostMalloc((void**)&b.host, bytes, hipHostMallocDefault));
     cap_ = bytes;
     return KLSH_OK;
   }
@@ -189,7 +172,7 @@ class DbWriter {
   }
   // a piece finished on the device: its kernel time, then its bytes to the file
   int drain(Buf& b, FILE* f, const std::string& path, uint64_t bytes, uint64_t* total) {
-    KLSH_CRET(hipEventSynchronize(b.done));
+    KLSH_HIP(hipEventSynchronize(b.done));
     float ms = 0.0f;
     (void)hipEventElapsedTime(&ms, b.e0, b.e1);
     st_.pack_ms += ms;
@@ -207,13 +190,13 @@ class DbWriter {
     auto start = [&](uint64_t r0) {  // chunk r0 / per packed and on its way to its pinned buffer
       Buf& b = buf_[(r0 / per) & 1];
       const uint64_t m = std::min<uint64_t>(per, n - r0);
-      KLSH_CRET(hipEventRecord(b.e0, s_));
+      KLSH_HIP(hipEventRecord(b.e0, s_));
       klsh::launch_kmcdb_pack(val, cnt, r0, m, sufix, dev_, s_,
                               hooks_.grid_cap);
-      KLSH_CRET(hipGetLastError());
-      KLSH_CRET(hipEventRecord(b.e1, s_));
-      KLSH_CRET(hipMemcpyAsync(b.host, dev_, m * rec, hipMemcpyDeviceToHost, s_));
-      KLSH_CRET(hipEventRecord(b.done, s_));
+      KLSH_HIP(hipGetLastError());
+      KLSH_HIP(hipEventRecord(b.e1, s_));
+      KLSH_HIP(hipMemcpyAsync(b.host, dev_, m * rec, hipMemcpyDeviceToHost, s_));
+      KLSH_HIP(hipEventRecord(b.done, s_));
       hooks_.db_chunks += 1;
       st_.chunks += 1;
       return (int)KLSH_OK;
@@ -236,13 +219,13 @@ class DbWriter {
     auto start = [&](uint64_t q0) {
       Buf& b = buf_[(q0 / per) & 1];
       const uint64_t mq = std::min<uint64_t>(per, entries - q0);
-      KLSH_CRET(hipEventRecord(b.e0, s_));
+      KLSH_HIP(hipEventRecord(b.e0, s_));
       klsh::launch_kmcdb_lut(val, n, q0, mq, k_, p, reinterpret_cast<uint64_t*>(dev_), s_,
                              hooks_.grid_cap);
-      KLSH_CRET(hipGetLastError());
-      KLSH_CRET(hipEventRecord(b.e1, s_));
-      KLSH_CRET(hipMemcpyAsync(b.host, dev_, mq * 8, hipMemcpyDeviceToHost, s_));
-      KLSH_CRET(hipEventRecord(b.done, s_));
+      KLSH_HIP(hipGetLastError());
+      KLSH_HIP(hipEventRecord(b.e1, s_));
+      KLSH_HIP(hipMemcpyAsync(b.host, dev_, mq * 8, hipMemcpyDeviceToHost, s_));
+      KLSH_HIP(hipEventRecord(b.done, s_));
       return (int)KLSH_OK;
     };
     if ((rc = start(0))) return rc;
@@ -264,7 +247,7 @@ class DbWriter {
 class Counter {
  public:
   Counter(klsh_ctx* ctx, int k, uint32_t count_min, klsh_kcount_stats& st)
-      : hooks_(klsh::ctx_kcount(ctx)), s_(klsh::ctx_stream(ctx)), k_(k), count_min_(count_min),
+      : hooks_(ctx->kcount), s_(ctx->stream), k_(k), count_min_(count_min),
         st_(st) {}
   ~Counter() {
     for (auto& sl : slot_) {
@@ -282,13 +265,13 @@ class Counter {
   int init() {
     cap_ = hooks_.table_slots ? hooks_.table_slots : kTableSlots;
     hooks_.peak_slots = cap_;
-    KLSH_CRET(hipMalloc((void**)&keys_, cap_ * 8));
-    KLSH_CRET(hipMalloc((void**)&cnt_, cap_ * 4));
-    KLSH_CRET(hipMalloc((void**)&ctr_, 64));
-    KLSH_CRET(hipHostMalloc((void**)&hctr_, 64, hipHostMallocDefault));
+    KLSH_HIP(hipMalloc((void**)&keys_, cap_ * 8));
+    KLSH_HIP(hipMalloc((void**)&cnt_, cap_ * 4));
+    KLSH_HIP(hipMalloc((void**)&ctr_, 64));
+    KLSH_HIP(hipHostMalloc((void**)&hctr_, 64, hipHostMallocDefault));
     for (auto& sl : slot_) {
-      KLSH_CRET(hipEventCreate(&sl.e0));
-      KLSH_CRET(hipEventCreate(&sl.e1));
+      KLSH_HIP(hipEventCreate(&sl.e0));
+      KLSH_HIP(hipEventCreate(&sl.e1));
     }
     return KLSH_OK;
   }
@@ -370,30 +353,30 @@ class Counter {
       if (sl.dseq) (void)hipFree(sl.dseq);
       sl.dseq = nullptr;
       sl.cap_b = 0;
-      KLSH_CRET(hipMalloc((void**)&sl.dseq, nb + nb / 4 + 64));
+      KLSH_HIP(hipMalloc((void**)&sl.dseq, nb + nb / 4 + 64));
       sl.cap_b = nb + nb / 4 + 64;
     }
     if (n + 1 > sl.cap_r) {
       if (sl.doff) (void)hipFree(sl.doff);
       sl.doff = nullptr;
       sl.cap_r = 0;
-      KLSH_CRET(hipMalloc((void**)&sl.doff, (n + 1) * 8));
+      KLSH_HIP(hipMalloc((void**)&sl.doff, (n + 1) * 8));
       sl.cap_r = n + 1;
     }
-    if (nb) KLSH_CRET(hipMemcpyAsync(sl.dseq, sl.seq.data(), nb, hipMemcpyHostToDevice, s_));
-    KLSH_CRET(hipMemcpyAsync(sl.doff, sl.off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s_));
-    KLSH_CRET(hipEventRecord(sl.e0, s_));
+    if (nb) KLSH_HIP(hipMemcpyAsync(sl.dseq, sl.seq.data(), nb, hipMemcpyHostToDevice, s_));
+    KLSH_HIP(hipMemcpyAsync(sl.doff, sl.off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s_));
+    KLSH_HIP(hipEventRecord(sl.e0, s_));
     klsh::launch_kcount_reads(sl.dseq, sl.doff, n, k_, keys_, cnt_, cap_ - 1, ctr_, s_,
                               hooks_.grid_cap);
-    KLSH_CRET(hipGetLastError());
-    KLSH_CRET(hipEventRecord(sl.e1, s_));
-    KLSH_CRET(hipMemcpyAsync(hctr_, ctr_, 16, hipMemcpyDeviceToHost, s_));
+    KLSH_HIP(hipGetLastError());
+    KLSH_HIP(hipEventRecord(sl.e1, s_));
+    KLSH_HIP(hipMemcpyAsync(hctr_, ctr_, 16, hipMemcpyDeviceToHost, s_));
     return KLSH_OK;
   }
 
   // the batch in flight finished: its kernel time, the table's load and the windows so far
   int finish(Slot& sl) {
-    KLSH_CRET(hipStreamSynchronize(s_));
+    KLSH_HIP(hipStreamSynchronize(s_));
     float ms = 0.0f;
     (void)hipEventElapsedTime(&ms, sl.e0, sl.e1);
     st_.kernel_ms += ms;
@@ -404,9 +387,9 @@ class Counter {
 
   int count(klsh_fastq* f) {
     occ_ = pos_ = 0;
-    KLSH_CRET(hipMemsetAsync(keys_, 0xFF, cap_ * 8, s_));
-    KLSH_CRET(hipMemsetAsync(cnt_, 0, cap_ * 4, s_));
-    KLSH_CRET(hipMemsetAsync(ctr_, 0, 64, s_));
+    KLSH_HIP(hipMemsetAsync(keys_, 0xFF, cap_ * 8, s_));
+    KLSH_HIP(hipMemsetAsync(cnt_, 0, cap_ * 4, s_));
+    KLSH_HIP(hipMemsetAsync(ctr_, 0, 64, s_));
     const uint64_t per = hooks_.batch_reads ? hooks_.batch_reads : kBatchReads;
     int cur = 0, rc = KLSH_OK;
     bool pending = false;
@@ -458,22 +441,22 @@ class Counter {
       val_ = nullptr;
       sort_cap_ = 0;
       const uint64_t c = occ_ + occ_ / 4 + 64;
-      KLSH_CRET(hipMalloc((void**)&lo_, c * 4));
-      KLSH_CRET(hipMalloc((void**)&lo2_, c * 4));
-      KLSH_CRET(hipMalloc((void**)&sl_, c * 4));
-      KLSH_CRET(hipMalloc((void**)&sl2_, c * 4));
-      KLSH_CRET(hipMalloc((void**)&ws_, klsh::sort_ws_words(c) * 4));
-      KLSH_CRET(hipMalloc((void**)&val_, c * 8));
+      KLSH_HIP(hipMalloc((void**)&lo_, c * 4));
+      KLSH_HIP(hipMalloc((void**)&lo2_, c * 4));
+      KLSH_HIP(hipMalloc((void**)&sl_, c * 4));
+      KLSH_HIP(hipMalloc((void**)&sl2_, c * 4));
+      KLSH_HIP(hipMalloc((void**)&ws_, klsh::sort_ws_words(c) * 4));
+      KLSH_HIP(hipMalloc((void**)&val_, c * 8));
       sort_cap_ = c;
     }
     uint32_t* nout = reinterpret_cast<uint32_t*>(ctr_ + 4);
     uint32_t n = 0;
-    KLSH_CRET(hipMemsetAsync(nout, 0, 4, s_));
+    KLSH_HIP(hipMemsetAsync(nout, 0, 4, s_));
     klsh::launch_kcount_collect(keys_, cnt_, cap_, count_min_, lo_, sl_, nout, s_,
                                 hooks_.grid_cap);
-    KLSH_CRET(hipGetLastError());
-    KLSH_CRET(hipMemcpyAsync(&n, nout, 4, hipMemcpyDeviceToHost, s_));
-    KLSH_CRET(hipStreamSynchronize(s_));
+    KLSH_HIP(hipGetLastError());
+    KLSH_HIP(hipMemcpyAsync(&n, nout, 4, hipMemcpyDeviceToHost, s_));
+    KLSH_HIP(hipStreamSynchronize(s_));
     // ascending KMC value: two stable 32-bit radix sorts, low word then high word
     uint32_t *ok = lo_, *ov = sl_;
     if (n) klsh::radix_sort(lo_, sl_, lo2_, sl2_, n, k_ < 16 ? 2 * k_ : 32, ws_, &ok, &ov, s_);
@@ -486,20 +469,20 @@ class Counter {
       klsh::radix_sort(hk, ov, ok, hv, n, 2 * k_ - 32, ws_, &ok2, &ov2, s_);
       ov = ov2;
     }
-    KLSH_CRET(hipGetLastError());
+    KLSH_HIP(hipGetLastError());
     out->n = n;
-    KLSH_CRET(hipMalloc((void**)&out->rep, (uint64_t)(n ? n : 1) * 8));
-    KLSH_CRET(hipMalloc((void**)&out->cnt, (uint64_t)(n ? n : 1) * 4));
+    KLSH_HIP(hipMalloc((void**)&out->rep, (uint64_t)(n ? n : 1) * 8));
+    KLSH_HIP(hipMalloc((void**)&out->cnt, (uint64_t)(n ? n : 1) * 4));
     klsh::launch_kcount_emit(keys_, cnt_, ov, n, k_, val_, out->rep, out->cnt, s_,
                              hooks_.grid_cap);
-    KLSH_CRET(hipGetLastError());
+    KLSH_HIP(hipGetLastError());
     std::vector<uint32_t> hcnt(n);
-    if (n) KLSH_CRET(hipMemcpyAsync(hcnt.data(), out->cnt, n * 4ull, hipMemcpyDeviceToHost, s_));
+    if (n) KLSH_HIP(hipMemcpyAsync(hcnt.data(), out->cnt, n * 4ull, hipMemcpyDeviceToHost, s_));
     if (keep_val) {
       keep_val->resize(n);
-      if (n) KLSH_CRET(hipMemcpyAsync(keep_val->data(), val_, n * 8ull, hipMemcpyDeviceToHost, s_));
+      if (n) KLSH_HIP(hipMemcpyAsync(keep_val->data(), val_, n * 8ull, hipMemcpyDeviceToHost, s_));
     }
-    KLSH_CRET(hipStreamSynchronize(s_));
+    KLSH_HIP(hipStreamSynchronize(s_));
     float cov = 0.0f;
     for (uint32_t i = 0; i < n; ++i) cov += log((double)hcnt[i]);
     out->coverage = cov;
@@ -514,7 +497,7 @@ class Counter {
 extern "C" int klsh_kcount_listing(klsh_ctx* ctx, int sample, uint64_t* kmc_values,
                                    uint32_t* counts, uint64_t* n) {
   if (!ctx || !n) return set_error(KLSH_E_ARG, "null argument");
-  const klsh::KcountHooks& h = klsh::ctx_kcount(ctx);
+  const klsh::KcountHooks& h = ctx->kcount;
   if (sample < 0 || (size_t)sample >= h.values.size())
     return set_error(KLSH_E_ARG, "klsh_kcount_listing: no kept listing of that sample");
   const std::vector<uint64_t>& v = h.values[sample];
@@ -545,8 +528,8 @@ int count_run(klsh_ctx* ctx, const char* const* fastq_paths, const char* const* 
   local.struct_size = sizeof(local);
   klsh_kmcdb_stats dlocal{};
   dlocal.struct_size = sizeof(dlocal);
-  klsh::KcountHooks& hooks = klsh::ctx_kcount(ctx);  // test hooks; what this call reaches
-  klsh::KmcHooks& bhooks = klsh::ctx_kmc(ctx);
+  klsh::KcountHooks& hooks = ctx->kcount;  // test hooks; what this call reaches
+  klsh::KmcHooks& bhooks = ctx->kmc;
   hooks.batches = hooks.rehashes = hooks.peak_slots = 0;
   hooks.db_chunks = 0;
   hooks.db_prefix_used = -1;
@@ -583,7 +566,7 @@ int count_run(klsh_ctx* ctx, const char* const* fastq_paths, const char* const* 
         if (!old) (void)remove(path.c_str());
       }
   }
-  if (hipSetDevice(klsh::ctx_device(ctx)) != hipSuccess) return set_error(KLSH_E_HIP, "hipSetDevice");
+  if (hipSetDevice(ctx->device) != hipSuccess) return set_error(KLSH_E_HIP, "hipSetDevice");
   int rc;
   {
     ListingSource src;

@@ -19,23 +19,13 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <chrono>
 #include <cmath>
 #include <string>
 #include <vector>
 
-#include "klsh.h"
-#include "klsh_internal.h"
+#include "klsh_ctx.h"
 
 namespace {
-
-using klsh::set_error;
-
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(
-             std::chrono::steady_clock::now().time_since_epoch())
-      .count();
-}
 
 // CKMCFile::OpenForListing + ReadParamsFrom_prefix_file_buf (kmc_file.cpp:66-300), restated.
 struct KmcDb {
@@ -331,7 +321,7 @@ extern "C" int klsh_cuckoo_order(const uint64_t* images, uint64_t n, int k, uint
 // klsh_build_khtable call in the order of their first ordinal, what CuckooOrder then replays.
 extern "C" int klsh_khtable_first(klsh_ctx* ctx, uint64_t* images, uint64_t* n) {
   if (!ctx || !n) return set_error(KLSH_E_ARG, "null argument");
-  const std::vector<uint64_t>& first = klsh::ctx_kmc(ctx).first;
+  const std::vector<uint64_t>& first = ctx->kmc.first;
   const uint64_t room = *n;
   *n = first.size();
   if (!images) return KLSH_OK;
@@ -340,19 +330,14 @@ extern "C" int klsh_khtable_first(klsh_ctx* ctx, uint64_t* images, uint64_t* n) 
   return KLSH_OK;
 }
 
-#define KLSH_KHIP(call)                                                                   \
-  do {                                                                                    \
-    hipError_t e_ = (call);                                                               \
-    if (e_ != hipSuccess) {                                                               \
-      rc = set_error(KLSH_E_HIP, (std::string(#call) + " -> " + hipGetErrorString(e_)).c_str()); \
-      goto done;                                                                          \
-    }                                                                                     \
-  } while (0)
-#define KLSH_KRET(call)                                                                   \
-  do {                                                                                    \
-    hipError_t e_ = (call);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return set_error(KLSH_E_HIP, (std::string(#call) + " -> " + hipGetErrorString(e_)).c_str()); \
+// KLSH_HIP for khtable_run, which releases its buffers at `done` instead of returning
+#define KLSH_KHIP(call)                      \
+  do {                                       \
+    hipError_t e_ = (call);                  \
+    if (e_ != hipSuccess) {                  \
+      rc = klsh::hip_fail(#call, e_);        \
+      goto done;                             \
+    }                                        \
   } while (0)
 
 namespace {
@@ -375,11 +360,11 @@ class KmcFileSource : public klsh::KhSource {
       max_lut = std::max<uint64_t>(max_lut, db.lut.size());
       max_chunk_recs = std::max<uint64_t>(max_chunk_recs, kChunkBytes / db.params().rec_size + 1);
     }
-    KLSH_KRET(hipMalloc((void**)&drec_, kChunkBytes + 64));
-    KLSH_KRET(hipMalloc((void**)&drep_, max_chunk_recs * 8));
-    KLSH_KRET(hipMalloc((void**)&dcnt_, max_chunk_recs * 4));
-    KLSH_KRET(hipMalloc((void**)&dlut_, max_lut * 8));
-    KLSH_KRET(hipMalloc((void**)&nvalid_, 64));
+    KLSH_HIP(hipMalloc((void**)&drec_, kChunkBytes + 64));
+    KLSH_HIP(hipMalloc((void**)&drep_, max_chunk_recs * 8));
+    KLSH_HIP(hipMalloc((void**)&dcnt_, max_chunk_recs * 4));
+    KLSH_HIP(hipMalloc((void**)&dlut_, max_lut * 8));
+    KLSH_HIP(hipMalloc((void**)&nvalid_, 64));
     return KLSH_OK;
   }
   uint64_t total(int j) const override { return dbs_[j].total; }
@@ -392,8 +377,8 @@ class KmcFileSource : public klsh::KhSource {
     const KmcDb& db = dbs_[j];
     kp_ = db.params();
     cov_ = 0.0f;
-    KLSH_KRET(hipMemcpyAsync(dlut_, db.lut.data(), db.lut.size() * 8, hipMemcpyHostToDevice, s));
-    KLSH_KRET(hipMemsetAsync(nvalid_, 0, 4, s));
+    KLSH_HIP(hipMemcpyAsync(dlut_, db.lut.data(), db.lut.size() * 8, hipMemcpyHostToDevice, s));
+    KLSH_HIP(hipMemsetAsync(nvalid_, 0, 4, s));
     f_ = fopen(db.suf.c_str(), "rb");
     if (!f_) return set_error(KLSH_E_ARG, ("cannot open " + db.suf).c_str());
     char mark[4];
@@ -408,7 +393,7 @@ class KmcFileSource : public klsh::KhSource {
     if (fread(hrec_.data(), kp_.rec_size, n, f_) != n)
       return set_error(KLSH_E_ARG, (db.suf + ": short file").c_str());
     st_.io_ms += now_ms() - tio;
-    KLSH_KRET(hipMemcpyAsync(drec_, hrec_.data(), n * kp_.rec_size, hipMemcpyHostToDevice, s));
+    KLSH_HIP(hipMemcpyAsync(drec_, hrec_.data(), n * kp_.rec_size, hipMemcpyHostToDevice, s));
     klsh::launch_kmc_decode(drec_, n, r0, kp_, dlut_, db.lut.size(), drep_, dcnt_, nvalid_, s,
                             hooks_.grid_cap);
     if (pass == 0) ++hooks_.decode_launches;
@@ -432,7 +417,7 @@ class KmcFileSource : public klsh::KhSource {
     st_.records += dbs_[j].total;
     if (pass == 0) {
       uint32_t nv = 0;
-      KLSH_KRET(hipMemcpy(&nv, nvalid_, 4, hipMemcpyDeviceToHost));
+      KLSH_HIP(hipMemcpy(&nv, nvalid_, 4, hipMemcpyDeviceToHost));
       *listed = nv;
     } else {
       *coverage = cov_;
@@ -458,9 +443,9 @@ class KmcFileSource : public klsh::KhSource {
 int klsh::khtable_run(klsh_ctx* ctx, klsh::KhSource& src, int n_samples, int k, const char* out_dir,
                       klsh_khtable_stats* st) {
   klsh_khtable_stats& local = *st;
-  klsh::KmcHooks& hooks = klsh::ctx_kmc(ctx);
+  klsh::KmcHooks& hooks = ctx->kmc;
   const uint32_t gc = hooks.grid_cap;  // option "grid_cap" (tests): workgroups per launch, at most
-  const hipStream_t s = klsh::ctx_stream(ctx);
+  const hipStream_t s = ctx->stream;
   const std::string dir = (out_dir && *out_dir) ? std::string(out_dir) + "/" : std::string();
   uint64_t records = 0;
   for (int j = 0; j < n_samples; ++j) records += src.total(j);
@@ -627,7 +612,7 @@ extern "C" int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, i
     return set_error(KLSH_E_ARG, "klsh_khtable_stats.struct_size != sizeof: built against another klsh.h");
   klsh_khtable_stats local{};
   local.struct_size = sizeof(local);
-  klsh::KmcHooks& hooks = klsh::ctx_kmc(ctx);  // test hooks; what this call reaches
+  klsh::KmcHooks& hooks = ctx->kmc;  // test hooks; what this call reaches
   hooks.decode_launches = 0;
   hooks.high_sort = 0;
   hooks.first.clear();
@@ -638,7 +623,7 @@ extern "C" int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, i
     if ((int)dbs[j].k != k)
       return set_error(KLSH_E_ARG, (std::string(kmc_names[j]) + ": k-mer length differs from -K").c_str());
   }
-  if (hipSetDevice(klsh::ctx_device(ctx)) != hipSuccess) return set_error(KLSH_E_HIP, "hipSetDevice");
+  if (hipSetDevice(ctx->device) != hipSuccess) return set_error(KLSH_E_HIP, "hipSetDevice");
   int rc;
   {
     KmcFileSource src(dbs, hooks, local);
