@@ -236,7 +236,9 @@ int klsh_comm_info(klsh_ctx* ctx, int* rank, int* world);
 int klsh_set_option(klsh_ctx* ctx, const char* name, int64_t value);
 /* Any option above, plus read-only diagnostics: "fp16_image" (1 = the loaded rows have the fp16
  * image), "last_hash_kernel" (klsh_hash_keys' projection kernel: 0 packed chains, 1 fp16-image
- * screen, 2 f32 fp16x3 wide-row screen, -1 none) and
+ * screen, 2 f32 fp16x3 wide-row screen, -1 none), "last_hash_variant" (the kernel itself: 0
+ * k_project_pk, 1 k_project_wide_pk, 2 k_project_generic, 3 k_project_h16, 4
+ * k_project_mfma_wide<512>, 5 k_project_mfma_wide<0>, -1 none) and
  * "last_hash_close_pairs" (its (row, hyperplane) pairs settled by the exact chains). */
 int klsh_get_option(klsh_ctx* ctx, const char* name, int64_t* value);
 

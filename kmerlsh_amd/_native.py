@@ -48,6 +48,14 @@ ABI_VERSION = 3
 KERNEL_CLASSES = ("project", "sort", "runs", "small", "big128", "big192", "big384", "big896",
                   "huge", "tail", "compact", "screen", "merge")
 KCLASSES = 13
+# option "last_hash_variant" (klsh_internal.h ProjVariant): the kernel klsh_hash_keys launched
+PROJ_VARIANT_NONE = -1
+PROJ_VARIANT_PK = 0             # k_project_pk<D>
+PROJ_VARIANT_WIDE_PK = 1        # k_project_wide_pk
+PROJ_VARIANT_GENERIC = 2        # k_project_generic
+PROJ_VARIANT_H16 = 3            # k_project_h16<D>
+PROJ_VARIANT_MFMA_WIDE_512 = 4  # k_project_mfma_wide<512> + k_project_fix
+PROJ_VARIANT_MFMA_WIDE = 5      # k_project_mfma_wide<0> + k_project_fix
 
 
 class KlshKstat(ctypes.Structure):

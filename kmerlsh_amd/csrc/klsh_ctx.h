@@ -244,6 +244,7 @@ struct klsh_ctx {
   // klsh_hash_keys diagnostics (klsh_get_option): the projection kernel of the last call and
   // the (row, hyperplane) pairs its screen left to the exact chains
   int last_hash_kernel = klsh::kPkNone;
+  int last_hash_variant = klsh::kPvNone;
   uint64_t last_hash_close = 0;
   // the result on the device: option "result_device" (klsh_count / klsh_result
   // through the offsets scan and the list ranking) and the ranking rounds of the last such result

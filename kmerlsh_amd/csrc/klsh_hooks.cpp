@@ -86,6 +86,7 @@ int klsh_hash_keys(klsh_ctx* ctx, const float* rows, uint64_t n, int d, const fl
   if (d <= 0 || d > 4096 || h < 0 || h > 31) return fail(KLSH_E_RANGE, "d or h out of range");
   if (n >= 0xFFFFFFF0ull) return fail(KLSH_E_RANGE, "rows >= 2^32");
   ctx->last_hash_kernel = klsh::kPkNone;
+  ctx->last_hash_variant = klsh::kPvNone;
   ctx->last_hash_close = 0;
   if (n == 0) return 0;
   KLSH_HIP(hipSetDevice(ctx->device));
@@ -126,7 +127,9 @@ int klsh_hash_keys(klsh_ctx* ctx, const float* rows, uint64_t n, int d, const fl
     rc = fail(KLSH_E_HIP, "upload");
   } else {
     if (image) klsh::launch_shadow_build(r, n, s);
-    const int kern = klsh::launch_project(r, slots, dkeys, (uint32_t)n, W, h, 0u, s, &pw);
+    int variant = klsh::kPvNone;
+    const int kern = klsh::launch_project(r, slots, dkeys, (uint32_t)n, W, h, 0u, s, &pw,
+                                          klsh::kNoTime, &variant);
     uint32_t w[64];
     if (hipGetLastError() != hipSuccess ||
         hipMemcpyAsync(keys, dkeys, 4 * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -135,6 +138,7 @@ int klsh_hash_keys(klsh_ctx* ctx, const float* rows, uint64_t n, int d, const fl
       rc = fail(KLSH_E_HIP, "projection");
     } else {
       ctx->last_hash_kernel = kern;
+      ctx->last_hash_variant = variant;
       ctx->last_hash_close = klsh::proj_close_pairs(w);
     }
   }

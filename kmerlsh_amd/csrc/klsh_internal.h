@@ -289,9 +289,21 @@ void launch_project_device_n(const Rows& r, const uint32_t* slots, uint32_t* key
 // pw (may be null): the workspace that enables the matrix-core screens (the fp16 row image where
 // r.xh is set, bf16x3 for d > 64).  Returns the kernel it launched (ProjKernel).
 enum ProjKernel : int { kPkNone = -1, kPkPacked = 0, kPkH16 = 1, kPkWide = 2 };
+// The kernel behind a ProjKernel (option "last_hash_variant"; mirrored in _native.py): the three
+// packed exact-chain kernels share kPkPacked, the two instantiations of the wide screen kPkWide.
+enum ProjVariant : int {
+  kPvNone = -1,
+  kPvPk = 0,          // k_project_pk<D> (d = 8, 16, 32, 64)
+  kPvWidePk = 1,      // k_project_wide_pk (hyperplanes in LDS: 16 dp ceil(h / 4) <= 64 KB)
+  kPvGeneric = 2,     // k_project_generic (hyperplanes from memory)
+  kPvH16 = 3,         // k_project_h16<D>
+  kPvMfmaWide512 = 4, // k_project_mfma_wide<512> + k_project_fix
+  kPvMfmaWide = 5,    // k_project_mfma_wide<0> + k_project_fix
+};
+// variant (may be null): receives the ProjVariant launched.
 int launch_project(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_t n,
                    const float* W, int h, uint32_t key_or, hipStream_t s,
-                   const ProjectWork* pw = nullptr, KTime kt = kNoTime);
+                   const ProjectWork* pw = nullptr, KTime kt = kNoTime, int* variant = nullptr);
 
 // Stable LSD radix sort of (keys, vals)[0..n) on the low `bits` bits (klsh_sort.hip); ping-pong
 // buffers, *out_k/*out_v = the pair holding the result.  ws: sort_ws_words(n) words.

@@ -967,7 +967,10 @@ void launch_project_device_n(const Rows& r, const uint32_t* slots, uint32_t* key
 // wide-row packed kernel with the hyperplanes in LDS, else the generic kernel.
 int launch_project(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_t n,
                     const float* W, int h, uint32_t key_or, hipStream_t s, const ProjectWork* pw,
-                    KTime kt) {
+                    KTime kt, int* variant) {
+  int pv_unused;
+  int& pv = variant ? *variant : pv_unused;
+  pv = kPvNone;
   if (n == 0) return kPkNone;
   const dim3 grid((n + 255) / 256), block(256);
   if (pw && pw->variant != kProjPacked && r.d > 64 && h > 0) {
@@ -991,6 +994,7 @@ int launch_project(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_
       // stamped as one span: the screen (start) and the fix-up of its close calls (end)
       KTime k1 = kt;
       k1.fold = -1;
+      pv = r.d == 512 && !pw->wide_rolled ? kPvMfmaWide512 : kPvMfmaWide;
       if (r.d == 512 && !pw->wide_rolled)  // option "wide_unrolled" (default 1)
         k_project_mfma_wide<512><<<gm, dim3(kWideNT), lds, s>>>(r.x, r.d, r.dp, slots, keys, n, W,
                                                                 h, key_or, wide_eps(r.d),
@@ -1006,11 +1010,13 @@ int launch_project(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_
   }
   if (h16_ok(r, pw) && h > 0) {
     launch_h16(r, slots, keys, n, W, h, key_or, s, *pw, kt, nullptr, nullptr);
+    pv = kPvH16;
     return kPkH16;
   }
   auto go_pk = [&](auto kern) {
     kern<<<grid, block, 0, s>>>(r.x, r.dp, slots, keys, n, W, h, key_or, nullptr, kt, nullptr);
   };
+  pv = kPvPk;
   switch (r.d) {
     case 8: go_pk(k_project_pk<8, 2, 1>); break;
     case 16: go_pk(k_project_pk<16, 2, 1>); break;
@@ -1025,7 +1031,9 @@ int launch_project(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_
         (void)lds_ok;
         k_project_wide_pk<1><<<grid, block, lds, s>>>(r.x, r.d, r.dp, slots, keys, n, W, h, key_or,
                                                       kt);
+        pv = kPvWidePk;
       } else {
+        pv = kPvGeneric;
         k_project_generic<<<grid, block, 0, s>>>(r.x, r.d, r.dp, slots, keys, n, W, h, key_or, kt);
       }
     }

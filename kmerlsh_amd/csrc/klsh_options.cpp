@@ -150,6 +150,7 @@ const Option kOptions[] = {
     READONLY("member_nodes", c->loaded ? c->members : 0),
     READONLY("fp16_image", c->rows.xh != nullptr),
     READONLY("last_hash_kernel", c->last_hash_kernel),
+    READONLY("last_hash_variant", c->last_hash_variant),
     READONLY("last_hash_close_pairs", c->last_hash_close),
 };
 

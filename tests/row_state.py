@@ -11,8 +11,8 @@ offsets say it must be.  No tolerances: a cache that is off by one ulp is a wron
 
 Also here: the seeded inputs of the state tests ("spread" single-bucket rows, "ladder" loop rows),
 the projection tests' adversarial rows, the result comparison and the options context manager,
-shared by test_gpu_parity.py, test_gpu_row_state.py, test_gpu_sharded.py and
-test_gpu_launch_geometry.py.
+shared by test_gpu_parity.py, test_gpu_row_state.py, test_gpu_sharded.py,
+test_gpu_launch_geometry.py and test_gpu_widths.py.
 """
 import numpy as np
 
@@ -235,7 +235,7 @@ def adversarial_rows(rng, n, d, w):
     rows[1] = 0.0
     rows[4] *= f(1e-30)
     rows[7] *= f(1e30)
-    rows[10, 3] = np.nan
+    rows[10, min(3, d - 1)] = np.nan  # (d < 4: the row's last column)
     rows[13] = -0.0
     for m, i in enumerate(range(2, min(n, 2 + 3 * h * 4), 3)):  # s == 0 exactly for hyperplane j
         j, k = m % h, (m * 7) % d

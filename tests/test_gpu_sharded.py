@@ -133,6 +133,7 @@ def clustered(rng, n, d, groups, noise):
     (2, 60000, 20, 300, 6, 1000000),     # generic kernels
     (4, 50000, 16, 3, 3, 5000),          # nested buckets on several ranks every iteration
     (8, 3000, 8, 40, 6, 1000000),        # more ranks than some key ranges have rows
+    (2, 6000, 1000, 300, 6, 1000000),    # wide rows past the wide screen's 752 columns
 ])
 def test_sharded_random_vs_single(engine, world, n, d, groups, iters, bthr):
     rng = np.random.default_rng(n + d + world)
