@@ -628,11 +628,11 @@ int klsh_load_counts(klsh_ctx* ctx, const uint16_t* counts, uint64_t n_total,
     lut.resize(65536);
     for (int c = 0; c < 65536; ++c) lut[c] = (float)std::log((double)c + 1.0);
   }
-  uint16_t* dcounts = nullptr;
-  float *dlut = nullptr, *dv = nullptr;
-  if (int e = dalloc(&dcounts, (size_t)bs * d)) return e;
-  if (int e = dalloc(&dlut, 65536)) { dfree(dcounts); return e; }
-  if (int e = dalloc(&dv, d)) { dfree(dcounts); dfree(dlut); return e; }
+  klsh::DevBuf<uint16_t> dcounts;
+  klsh::DevBuf<float> dlut, dv;
+  if (int e = dalloc(dcounts, (size_t)bs * d)) return e;
+  if (int e = dalloc(dlut, 65536)) return e;
+  if (int e = dalloc(dv, d)) return e;
   auto convert = [&]() -> int {
     if (bs && hipMemcpy2DAsync(dcounts, sizeof(uint16_t) * bs, counts + batch_offset,
                                sizeof(uint16_t) * n_total, sizeof(uint16_t) * bs, d,
@@ -650,9 +650,6 @@ int klsh_load_counts(klsh_ctx* ctx, const uint16_t* counts, uint64_t n_total,
   };
   const int rc = convert();
   (void)hipStreamSynchronize(s);
-  dfree(dcounts);
-  dfree(dlut);
-  dfree(dv);
   if (rc) return rc;
   ctx->ids.resize(bs);
   for (uint64_t i = 0; i < bs; ++i) ctx->ids[i] = batch_offset + i;

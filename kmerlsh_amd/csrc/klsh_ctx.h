@@ -10,6 +10,7 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <memory>
 #include <string>
 #include <thread>
 #include <utility>
@@ -54,6 +55,69 @@ void dfree(T*& p) {
   if (p) (void)hipFree((void*)p);
   p = nullptr;
 }
+
+// Owners of what a function or an object allocates for its own lifetime: device memory, pinned
+// host memory, an event, an open file.  Move-only; the destructor releases.  (The long-lived
+// members of klsh_ctx, Rows, MergeWork and Snapshot stay raw pointers: they are passed to kernels
+// by value and released in release().)
+template <class T, bool Pinned = false>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.release()) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    reset(o.release());
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  // `count` elements (one at least) in place of what was held
+  hipError_t alloc(size_t count) {
+    reset();
+    const size_t bytes = sizeof(T) * (count ? count : 1);
+    const hipError_t e = Pinned ? hipHostMalloc((void**)&p_, bytes, hipHostMallocDefault)
+                                : hipMalloc((void**)&p_, bytes);
+    if (e != hipSuccess) p_ = nullptr;
+    return e;
+  }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+  T* release() { return std::exchange(p_, nullptr); }
+  void reset(T* p = nullptr) {
+    if (p_) (void)(Pinned ? hipHostFree((void*)p_) : hipFree((void*)p_));
+    p_ = p;
+  }
+
+ private:
+  T* p_ = nullptr;
+};
+template <class T>
+using PinBuf = DevBuf<T, true>;
+
+template <class T>  // dalloc's error for an owned buffer
+int dalloc(DevBuf<T>& b, size_t count) {
+  if (b.alloc(count) == hipSuccess) return 0;
+  return fail(KLSH_E_NOMEM, "hipMalloc of " + std::to_string(sizeof(T) * (count ? count : 1)) + " bytes");
+}
+
+class Event {
+ public:
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() {
+    if (e_) (void)hipEventDestroy(e_);
+  }
+  hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e_, flags); }
+  operator hipEvent_t() const { return e_; }
+
+ private:
+  hipEvent_t e_ = nullptr;
+};
+
+struct FileClose {
+  void operator()(FILE* f) const { (void)fclose(f); }
+};
+using File = std::unique_ptr<FILE, FileClose>;
 
 // The (row, hyperplane) pairs the certified projection screens left to the exact chains, from a
 // copy of ProjectWork::ws: ws[4..6) the wide-row fix-up kernel's total, ws[32..64) the fp16
@@ -116,6 +180,44 @@ using klsh::set_error;
     hipError_t e_ = (call);                                   \
     if (e_ != hipSuccess) return klsh::hip_fail(#call, e_);   \
   } while (0)
+
+namespace klsh {
+
+// One batch of reads on the device (modes E and K): the bases, the n + 1
+// read offsets, and the event pair around the batch's kernel.  Each buffer is replaced when a
+// batch does not fit; how large the new sequence buffer is, is the caller's rule.
+struct ReadBatch {
+  DevBuf<uint8_t> seq;
+  DevBuf<uint64_t> off;
+  uint64_t cap_b = 0, cap_r = 0;  // bytes of seq, entries of off
+  Event e0, e1;
+
+  int init() {
+    KLSH_HIP(e0.create());
+    KLSH_HIP(e1.create());
+    return KLSH_OK;
+  }
+  // nb bases and the offsets of n reads queued for upload; a sequence buffer that does not hold
+  // nb + 64 bytes is replaced by one of grow_bytes
+  int upload(const void* hseq, uint64_t nb, const uint64_t* hoff, uint64_t n, uint64_t grow_bytes,
+             hipStream_t s) {
+    if (nb + 64 > cap_b) {
+      cap_b = 0;
+      KLSH_HIP(seq.alloc(grow_bytes));
+      cap_b = grow_bytes;
+    }
+    if (n + 1 > cap_r) {
+      cap_r = 0;
+      KLSH_HIP(off.alloc(n + 1));
+      cap_r = n + 1;
+    }
+    if (nb) KLSH_HIP(hipMemcpyAsync(seq, hseq, nb, hipMemcpyHostToDevice, s));
+    KLSH_HIP(hipMemcpyAsync(off, hoff, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    return KLSH_OK;
+  }
+};
+
+}  // namespace klsh
 
 struct klsh_ctx {
   using Counters = klsh::Counters;

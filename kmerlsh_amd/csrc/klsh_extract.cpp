@@ -19,6 +19,7 @@
 #include <string.h>
 #include <zlib.h>
 
+#include <algorithm>
 #include <cmath>
 #include <string>
 #include <vector>
@@ -517,7 +518,7 @@ struct klsh_fastq {
 
 struct klsh_kset {
   klsh_ctx* ctx = nullptr;
-  uint64_t* tab = nullptr;
+  klsh::DevBuf<uint64_t> tab;
   uint64_t mask = 0;
   uint64_t n = 0;
 };
@@ -597,33 +598,27 @@ klsh_kset* klsh_kset_create(klsh_ctx* ctx, const uint64_t* kmers, uint64_t n, in
   const hipStream_t s = ctx->stream;
   uint64_t cap = 1024;
   while (cap < 2 * n) cap <<= 1;  // load factor <= 1/2
-  klsh_kset* ks = new klsh_kset();
+  std::unique_ptr<klsh_kset> ks(new klsh_kset());
   ks->ctx = ctx;
   ks->mask = cap - 1;
   ks->n = n;
-  uint64_t* dk = nullptr;
-  bool ok = hipMalloc((void**)&ks->tab, cap * 8) == hipSuccess;
-  ok = ok && (n == 0 || hipMalloc((void**)&dk, n * 8) == hipSuccess);
+  klsh::DevBuf<uint64_t> dk;
+  bool ok = ks->tab.alloc(cap) == hipSuccess;
+  ok = ok && (n == 0 || dk.alloc(n) == hipSuccess);
   ok = ok && hipMemsetAsync(ks->tab, 0xFF, cap * 8, s) == hipSuccess;
   ok = ok && (n == 0 || hipMemcpyAsync(dk, kmers, n * 8, hipMemcpyHostToDevice, s) == hipSuccess);
   if (ok) {
     klsh::launch_kset_insert(dk, n, ks->tab, ks->mask, s, ctx->mw.grid_cap);
     ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
   }
-  if (dk) (void)hipFree(dk);
-  if (!ok) {
-    if (ks->tab) (void)hipFree(ks->tab);
-    delete ks;
-    return bad(set_error(KLSH_E_NOMEM, "k-mer set allocation / upload failed"));
-  }
+  if (!ok) return bad(set_error(KLSH_E_NOMEM, "k-mer set allocation / upload failed"));
   if (err) *err = KLSH_OK;
-  return ks;
+  return ks.release();
 }
 
 void klsh_kset_destroy(klsh_kset* ks) {
   if (!ks) return;
   (void)hipSetDevice(ks->ctx->device);
-  if (ks->tab) (void)hipFree(ks->tab);
   delete ks;
 }
 
@@ -639,28 +634,18 @@ int klsh_check_reads(klsh_ctx* ctx, const klsh_kset* ks, const char* seq,
   const uint64_t nb = read_offsets[n_reads] - read_offsets[0];
   std::vector<uint64_t> off(read_offsets, read_offsets + n_reads + 1);
   for (auto& o : off) o -= read_offsets[0];
-  uint8_t *dseq = nullptr, *dflag = nullptr;
-  uint64_t* doff = nullptr;
-  uint32_t* dhit = nullptr;
-  bool ok = hipMalloc((void**)&dseq, nb + 64) == hipSuccess &&
-            hipMalloc((void**)&doff, (n_reads + 1) * 8) == hipSuccess &&
-            hipMalloc((void**)&dhit, n_reads * 4) == hipSuccess &&
-            hipMalloc((void**)&dflag, n_reads) == hipSuccess;
-  ok = ok && hipMemcpyAsync(dseq, seq + read_offsets[0], nb, hipMemcpyHostToDevice, s) == hipSuccess &&
-       hipMemcpyAsync(doff, off.data(), off.size() * 8, hipMemcpyHostToDevice, s) == hipSuccess;
-  if (ok) {
-    klsh::launch_check_reads(dseq, doff, n_reads, k, kmer_vote, ks->tab, ks->mask, dhit, dflag, s,
-                             ctx->mw.grid_cap);
-    ok = hipGetLastError() == hipSuccess;
-  }
-  ok = ok && (!hits || hipMemcpyAsync(hits, dhit, n_reads * 4, hipMemcpyDeviceToHost, s) == hipSuccess) &&
-       hipMemcpyAsync(flags, dflag, n_reads, hipMemcpyDeviceToHost, s) == hipSuccess &&
-       hipStreamSynchronize(s) == hipSuccess;
-  (void)hipFree(dseq);
-  (void)hipFree(doff);
-  (void)hipFree(dhit);
-  (void)hipFree(dflag);
-  if (!ok) return set_error(KLSH_E_HIP, "check_reads: allocation, copy or launch failed");
+  klsh::ReadBatch b;  // the call's one batch
+  klsh::DevBuf<uint32_t> dhit;
+  klsh::DevBuf<uint8_t> dflag;
+  KLSH_HIP(dhit.alloc(n_reads));
+  KLSH_HIP(dflag.alloc(n_reads));
+  if (int rc = b.upload(seq + read_offsets[0], nb, off.data(), n_reads, nb + 64, s)) return rc;
+  klsh::launch_check_reads(b.seq, b.off, n_reads, k, kmer_vote, ks->tab, ks->mask, dhit, dflag, s,
+                           ctx->mw.grid_cap);
+  KLSH_HIP(hipGetLastError());
+  if (hits) KLSH_HIP(hipMemcpyAsync(hits, dhit, n_reads * 4, hipMemcpyDeviceToHost, s));
+  KLSH_HIP(hipMemcpyAsync(flags, dflag, n_reads, hipMemcpyDeviceToHost, s));
+  KLSH_HIP(hipStreamSynchronize(s));
   return KLSH_OK;
 }
 
@@ -678,46 +663,26 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
   const hipStream_t s = ctx->stream;
   FastqReader rdr;
   if (!rdr.open(in_path)) return set_error(KLSH_E_ARG, (std::string("cannot open ") + in_path).c_str());
-  FILE* of = fopen(out_path, "wb");
+  klsh::File of(fopen(out_path, "wb"));
   if (!of) return set_error(KLSH_E_ARG, (std::string("cannot open for writing ") + out_path).c_str());
   // Two batch slots: the host parses batch i+1 (slot (i+1)&1) while the GPU checks batch i.
   constexpr uint64_t kReads = 1u << 18, kBases = 64ull << 20;
   struct Slot {
-    uint8_t* dseq = nullptr;
-    uint64_t* doff = nullptr;
-    uint32_t* dhit = nullptr;
-    uint8_t* dflag = nullptr;
-    uint8_t* hflag = nullptr;
-    uint64_t cap_b = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipEvent_t done = nullptr;  // after the flag copy: finish() waits for this batch only
+    klsh::PinBuf<uint8_t> hflag;  // (first: freed after the device buffers, whose release waits)
+    klsh::ReadBatch dev;
+    klsh::DevBuf<uint32_t> dhit;
+    klsh::DevBuf<uint8_t> dflag;
+    klsh::Event done;  // after the flag copy: finish() waits for this batch only
     uint64_t n = 0;
   } slot[2];
   int rc = KLSH_OK;
-  auto cleanup = [&]() {
-    for (auto& sl : slot) {
-      if (sl.dseq) (void)hipFree(sl.dseq);
-      if (sl.doff) (void)hipFree(sl.doff);
-      if (sl.dhit) (void)hipFree(sl.dhit);
-      if (sl.dflag) (void)hipFree(sl.dflag);
-      if (sl.hflag) (void)hipHostFree(sl.hflag);
-      if (sl.e0) (void)hipEventDestroy(sl.e0);
-      if (sl.e1) (void)hipEventDestroy(sl.e1);
-      if (sl.done) (void)hipEventDestroy(sl.done);
-    }
-  };
   for (auto& sl : slot) {
-    bool ok = hipMalloc((void**)&sl.doff, (kReads + 1) * 8) == hipSuccess &&
-              hipMalloc((void**)&sl.dhit, kReads * 4) == hipSuccess &&
-              hipMalloc((void**)&sl.dflag, kReads) == hipSuccess &&
-              hipHostMalloc((void**)&sl.hflag, kReads, hipHostMallocDefault) == hipSuccess &&
-              hipEventCreate(&sl.e0) == hipSuccess && hipEventCreate(&sl.e1) == hipSuccess &&
-              hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-      cleanup();
-      fclose(of);
-      return set_error(KLSH_E_NOMEM, "extract: batch buffers");
-    }
+    bool ok = sl.dev.off.alloc(kReads + 1) == hipSuccess && sl.dhit.alloc(kReads) == hipSuccess &&
+              sl.dflag.alloc(kReads) == hipSuccess && sl.hflag.alloc(kReads) == hipSuccess &&
+              sl.dev.e0.create() == hipSuccess && sl.dev.e1.create() == hipSuccess &&
+              sl.done.create(hipEventDisableTiming) == hipSuccess;
+    if (!ok) return set_error(KLSH_E_NOMEM, "extract: batch buffers");
+    sl.dev.cap_r = kReads + 1;  // every batch's offsets fit
   }
   // The reader parses every batch; its storage is swapped into a per-slot copy so the next parse
   // can proceed while the previous batch's records wait for their flags.
@@ -729,19 +694,14 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
     FastqReader& b = keep[si];
     sl.n = b.seq_off.size() - 1;
     const uint64_t nb = b.seq.size();
-    if (nb + 64 > sl.cap_b) {
-      if (sl.dseq) (void)hipFree(sl.dseq);
-      sl.dseq = nullptr;
-      sl.cap_b = nb + 64 > kBases + (64u << 10) ? nb + 64 : kBases + (64u << 10);
-      KLSH_HIP(hipMalloc((void**)&sl.dseq, sl.cap_b));
-    }
-    if (nb) KLSH_HIP(hipMemcpyAsync(sl.dseq, b.seq.data(), nb, hipMemcpyHostToDevice, s));
-    KLSH_HIP(hipMemcpyAsync(sl.doff, b.seq_off.data(), (sl.n + 1) * 8, hipMemcpyHostToDevice, s));
-    KLSH_HIP(hipEventRecord(sl.e0, s));
-    klsh::launch_check_reads(sl.dseq, sl.doff, sl.n, k, kmer_vote, ks->tab, ks->mask, sl.dhit,
+    if (int e = sl.dev.upload(b.seq.data(), nb, b.seq_off.data(), sl.n,
+                              std::max<uint64_t>(nb + 64, kBases + (64u << 10)), s))
+      return e;
+    KLSH_HIP(hipEventRecord(sl.dev.e0, s));
+    klsh::launch_check_reads(sl.dev.seq, sl.dev.off, sl.n, k, kmer_vote, ks->tab, ks->mask, sl.dhit,
                              sl.dflag, s, ctx->mw.grid_cap);
     KLSH_HIP(hipGetLastError());
-    KLSH_HIP(hipEventRecord(sl.e1, s));
+    KLSH_HIP(hipEventRecord(sl.dev.e1, s));
     KLSH_HIP(hipMemcpyAsync(sl.hflag, sl.dflag, sl.n, hipMemcpyDeviceToHost, s));
     KLSH_HIP(hipEventRecord(sl.done, s));
     return KLSH_OK;
@@ -749,9 +709,9 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
   auto finish = [&](int si) -> int {
     Slot& sl = slot[si];
     FastqReader& b = keep[si];
-    KLSH_HIP(hipEventSynchronize(sl.e1));
+    KLSH_HIP(hipEventSynchronize(sl.dev.e1));
     float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, sl.e0, sl.e1);
+    (void)hipEventElapsedTime(&ms, sl.dev.e0, sl.dev.e1);
     local.kernel_ms += ms;
     // the flag copy behind this batch's kernel — not the stream, which by now also holds the next
     // batch: waiting for that would serialise the host parse behind every kernel
@@ -783,7 +743,7 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
       out.insert(out.end(), b.qual.data() + b.qual_off[i], b.qual.data() + b.qual_off[i + 1]);
       out.push_back('\n');
     }
-    if (!out.empty() && fwrite(out.data(), 1, out.size(), of) != out.size())
+    if (!out.empty() && fwrite(out.data(), 1, out.size(), of.get()) != out.size())
       return set_error(KLSH_E_ARG, "extract: write failed");
     return KLSH_OK;
   };
@@ -810,8 +770,8 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
     cur ^= 1;
   }
   if (rc == KLSH_OK && pending) rc = finish(cur);
-  cleanup();
-  if (fclose(of) != 0 && rc == KLSH_OK) rc = set_error(KLSH_E_ARG, "extract: close failed");
+  if (rc) (void)hipStreamSynchronize(s);  // nothing of this call stays queued on its buffers
+  if (fclose(of.release()) != 0 && rc == KLSH_OK) rc = set_error(KLSH_E_ARG, "extract: close failed");
   local.total_ms = now_ms() - t_start;
   if (st) *st = local;
   return rc;

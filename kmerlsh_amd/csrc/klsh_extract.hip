@@ -10,9 +10,7 @@
 // [2i, 2i+2), A/C/G/T = 0/1/2/3 and every other character 0 (Kmer::set_kmer's switch, :115-135).
 // memcmp order of the bytes is the order of the byte-swapped word.
 //
-//   k_kset_insert  open-addressing table (linear probing, 64-bit CAS), the set's k-mers as read
-//                  from kmer_set.hex; the all-ones word is the empty marker (never a canonical
-//                  rep: the all-T k-mer's twin is 0)
+//   k_kset_insert  the set's k-mers as read from kmer_set.hex, into the k-mer table (klsh_kmer.h)
 //   k_check_reads  one wave per read: the read's bases staged as 2-bit codes in LDS (one byte
 //                  each), one lane per k-mer position building its word from LDS, reverse
 //                  complement with bit operations, one probe sequence per lane, a wave sum of the
@@ -26,34 +24,20 @@
 #include <stdint.h>
 
 #include "klsh_internal.h"
+#include "klsh_kmer.h"
 
 namespace klsh {
 
-constexpr uint64_t kKsetEmpty = ~0ull;
 constexpr int kCheckWaves = 4;        // waves per workgroup, each on its own reads
 constexpr uint32_t kCheckWindow = 2048;  // k-mer positions per LDS window (per wave)
-
-__device__ __forceinline__ uint64_t fmix64(uint64_t k) {  // murmur3 finalizer
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return k;
-}
 
 __global__ __launch_bounds__(256) void k_kset_insert(const uint64_t* __restrict__ kmers, uint64_t n,
                                                      unsigned long long* __restrict__ tab,
                                                      uint64_t mask) {
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull) {
     const unsigned long long key = kmers[i];
-    if (key == kKsetEmpty) continue;  // cannot be a canonical rep: never looked up
-    uint64_t h = fmix64(key) & mask;
-    while (true) {
-      const unsigned long long prev = atomicCAS(&tab[h], (unsigned long long)kKsetEmpty, key);
-      if (prev == kKsetEmpty || prev == key) break;
-      h = (h + 1) & mask;
-    }
+    if (key == kKtabEmpty) continue;  // cannot be a canonical rep: never looked up
+    (void)ktab_claim(tab, mask, key);
   }
 }
 
@@ -68,17 +52,6 @@ __device__ __forceinline__ uint64_t revcomp(uint64_t v, int k) {
 
 __device__ __forceinline__ uint32_t base_code(uint32_t c) {  // set_kmer / forwardBase switch
   return c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 0u;
-}
-
-__device__ __forceinline__ bool kset_has(const uint64_t* __restrict__ tab, uint64_t mask,
-                                         uint64_t key) {
-  uint64_t h = fmix64(key) & mask;
-  while (true) {
-    const uint64_t t = tab[h];
-    if (t == key) return true;
-    if (t == kKsetEmpty) return false;
-    h = (h + 1) & mask;
-  }
 }
 
 __global__ __launch_bounds__(256) void k_check_reads(const uint8_t* __restrict__ seq,
@@ -116,7 +89,7 @@ __global__ __launch_bounds__(256) void k_check_reads(const uint8_t* __restrict__
         v &= kmask;
         const uint64_t t = revcomp(v, k);
         const uint64_t key = __builtin_bswap64(v) < __builtin_bswap64(t) ? v : t;
-        cnt += kset_has(tab, mask, key) ? 1u : 0u;
+        cnt += ktab_find<false>(tab, mask, key) ? 1u : 0u;
       }
     }
 #pragma unroll
@@ -132,8 +105,7 @@ __global__ __launch_bounds__(256) void k_check_reads(const uint8_t* __restrict__
 void launch_kset_insert(const uint64_t* kmers, uint64_t n, uint64_t* tab, uint64_t mask,
                         hipStream_t s, uint32_t grid_cap) {
   if (n == 0) return;
-  const uint64_t g = (n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192;
-  k_kset_insert<<<cap_grid((uint32_t)g, grid_cap), 256, 0, s>>>(
+  k_kset_insert<<<stride_grid(n, grid_cap, 8192), 256, 0, s>>>(
       kmers, n, reinterpret_cast<unsigned long long*>(tab), mask);
 }
 

@@ -8,6 +8,7 @@
 #include "klsh_loop.h"
 
 using klsh::Counters;
+using klsh::DevBuf;
 using klsh::Rows;
 
 extern "C" {
@@ -94,24 +95,21 @@ int klsh_hash_keys(klsh_ctx* ctx, const float* rows, uint64_t n, int d, const fl
   Rows r{};
   r.d = d;
   r.dp = dp;
-  uint32_t *slots = nullptr, *dkeys = nullptr;
-  float* W = nullptr;
-  uint16_t* xh = nullptr;
-  klsh::ProjectWork pw = ctx->pw;  // the context's launch options, fresh workspaces
-  pw.fix = nullptr;
-  pw.ws = nullptr;
-  auto release = [&] {
-    dfree(r.x); dfree(slots); dfree(dkeys); dfree(W); dfree(pw.fix); dfree(pw.ws); dfree(xh);
-  };
+  DevBuf<float> x, W;
+  DevBuf<uint32_t> slots, dkeys, ws;
+  DevBuf<uint2> fix;
+  DevBuf<uint16_t> xh;
   int e = 0;
   const bool image = ctx->shadow_wanted(d);
-  if ((e = dalloc(&r.x, n * dp)) || (e = dalloc(&slots, n)) || (e = dalloc(&dkeys, n)) ||
-      (e = dalloc(&W, (uint64_t)std::max(h, 1) * dp)) || (e = dalloc(&pw.fix, n)) ||
-      (e = dalloc(&pw.ws, 64)) || (image && (e = dalloc(&xh, n * dp)))) {
-    release();
+  if ((e = dalloc(x, n * dp)) || (e = dalloc(slots, n)) || (e = dalloc(dkeys, n)) ||
+      (e = dalloc(W, (uint64_t)std::max(h, 1) * dp)) || (e = dalloc(fix, n)) ||
+      (e = dalloc(ws, 64)) || (image && (e = dalloc(xh, n * dp))))
     return e;
-  }
+  klsh::ProjectWork pw = ctx->pw;  // the context's launch options, fresh workspaces
+  pw.fix = fix;
+  pw.ws = ws;
   pw.cap = (uint32_t)n;
+  r.x = x;
   r.xh = xh;
   hipStream_t s = ctx->stream;
   std::vector<uint32_t> iota(n);
@@ -143,7 +141,6 @@ int klsh_hash_keys(klsh_ctx* ctx, const float* rows, uint64_t n, int d, const fl
     }
   }
   (void)hipStreamSynchronize(s);
-  release();
   return rc;
 }
 
@@ -154,19 +151,13 @@ int klsh_bucket_sort(klsh_ctx* ctx, const uint32_t* keys, uint64_t n, int bits,
   if (n >= 0xFFFFFFF0ull) return fail(KLSH_E_RANGE, "keys >= 2^32");
   if (n == 0) return 0;
   KLSH_HIP(hipSetDevice(ctx->device));
-  uint32_t *k0 = nullptr, *v0 = nullptr, *k1 = nullptr, *v1 = nullptr, *ws = nullptr, *ts = nullptr;
-  Counters* ctr = nullptr;
+  DevBuf<uint32_t> k0, v0, k1, v1, ws, ts;
+  DevBuf<Counters> ctr;
   const uint64_t ts_words = klsh::scan_ws_words(n);
   int e = 0;
-  auto release = [&] {
-    dfree(k0); dfree(v0); dfree(k1); dfree(v1); dfree(ws); dfree(ts); dfree(ctr);
-  };
-  if ((e = dalloc(&k0, n)) || (e = dalloc(&v0, n)) || (e = dalloc(&k1, n)) || (e = dalloc(&v1, n)) ||
-      (e = dalloc(&ws, klsh::sort_ws_words(n))) || (e = dalloc(&ts, ts_words)) ||
-      (e = dalloc(&ctr, 1))) {
-    release();
+  if ((e = dalloc(k0, n)) || (e = dalloc(v0, n)) || (e = dalloc(k1, n)) || (e = dalloc(v1, n)) ||
+      (e = dalloc(ws, klsh::sort_ws_words(n))) || (e = dalloc(ts, ts_words)) || (e = dalloc(ctr, 1)))
     return e;
-  }
   hipStream_t s = ctx->stream;
   std::vector<uint32_t> iota(n);
   for (uint64_t i = 0; i < n; ++i) iota[i] = (uint32_t)i;
@@ -191,7 +182,6 @@ int klsh_bucket_sort(klsh_ctx* ctx, const uint32_t* keys, uint64_t n, int bits,
       rc = fail(KLSH_E_HIP, "device protocol failure in the sort");
   }
   (void)hipStreamSynchronize(s);
-  release();
   return rc;
 }
 
@@ -207,33 +197,29 @@ int klsh_bucket_runs(klsh_ctx* ctx, const uint32_t* sorted_keys, uint64_t n, int
   KLSH_HIP(hipSetDevice(ctx->device));
   using klsh::kBigClasses;
   using klsh::kGroupClasses;
-  klsh::MergeWork w{};
-  uint32_t* dk = nullptr;
-  klsh::RunCounters* rc = nullptr;
-  auto release = [&] {
-    dfree(dk); dfree(rc); dfree(w.run_ws); dfree(w.huge); dfree(w.over);
-    for (auto& c : w.cls) dfree(c);
-    for (auto& c : w.big) dfree(c);
-  };
+  DevBuf<uint32_t> dk, run_ws;
+  DevBuf<klsh::RunCounters> rc;
+  DevBuf<uint2> huge, over, cls[kGroupClasses], big[kBigClasses];
   int e = 0;
-  if ((e = dalloc(&dk, n)) || (e = dalloc(&rc, 1)) || (e = dalloc(&w.run_ws, klsh::run_ws_words(n))) ||
-      (e = dalloc(&w.huge, n / 897 + 64)) || (e = dalloc(&w.over, n / 2 + 64))) {
-    release();
+  if ((e = dalloc(dk, n)) || (e = dalloc(rc, 1)) || (e = dalloc(run_ws, klsh::run_ws_words(n))) ||
+      (e = dalloc(huge, n / 897 + 64)) || (e = dalloc(over, n / 2 + 64)))
     return e;
-  }
-  for (int c = 0; c < kGroupClasses && !e; ++c) e = dalloc(&w.cls[c], klsh::group_class_capacity(c, n));
+  for (int c = 0; c < kGroupClasses && !e; ++c) e = dalloc(cls[c], klsh::group_class_capacity(c, n));
   for (int c = 0; c < kBigClasses && !e; ++c)
-    e = dalloc(&w.big[c], n / ((c ? klsh::kBigRows[c - 1] : 64) + 1) + 64);
-  if (e) {
-    release();
-    return e;
-  }
+    e = dalloc(big[c], n / ((c ? klsh::kBigRows[c - 1] : 64) + 1) + 64);
+  if (e) return e;
+  klsh::MergeWork w{};
+  w.run_ws = run_ws;
+  w.huge = huge;
+  w.over = over;
+  for (int c = 0; c < kGroupClasses; ++c) w.cls[c] = cls[c];
+  for (int c = 0; c < kBigClasses; ++c) w.big[c] = big[c];
   w.rc = rc;
   w.kt = klsh::kNoTime;
   hipStream_t s = ctx->stream;
   klsh::RunCounters hc{};
   int rc_ = 0;
-  if (hipMemsetAsync(rc, 0, sizeof(*rc), s) != hipSuccess ||
+  if (hipMemsetAsync(rc, 0, sizeof(hc), s) != hipSuccess ||
       hipMemcpyAsync(dk, sorted_keys, 4 * n, hipMemcpyHostToDevice, s) != hipSuccess) {
     rc_ = fail(KLSH_E_HIP, "upload");
   } else {
@@ -255,7 +241,6 @@ int klsh_bucket_runs(klsh_ctx* ctx, const uint32_t* sorted_keys, uint64_t n, int
   for (int c = 0; c < kBigClasses && !rc_; ++c) rc_ = take(w.big[c], hc.n_big[c].v, kGroupClasses + c);
   if (!rc_) rc_ = take(w.huge, hc.n_huge.v, klsh::kRunListCount - 2);
   if (!rc_) rc_ = take(w.over, hc.n_over.v, klsh::kRunListCount - 1);
-  release();
   if (rc_) return rc_;
   std::sort(runs.begin(), runs.end());
   *n_runs = runs.size();
@@ -299,12 +284,9 @@ int klsh_fp_selftest(klsh_ctx* ctx, const float* a, const float* b, uint64_t n, 
   if (!ctx || !a || !b || !sqrt_out || !div_out) return fail(KLSH_E_ARG, "null argument");
   if (n == 0) return 0;
   KLSH_HIP(hipSetDevice(ctx->device));
-  float *da = nullptr, *db = nullptr, *ds = nullptr, *dd = nullptr;
+  DevBuf<float> da, db, ds, dd;
   int e = 0;
-  if ((e = dalloc(&da, n)) || (e = dalloc(&db, n)) || (e = dalloc(&ds, n)) || (e = dalloc(&dd, n))) {
-    dfree(da); dfree(db); dfree(ds); dfree(dd);
-    return e;
-  }
+  if ((e = dalloc(da, n)) || (e = dalloc(db, n)) || (e = dalloc(ds, n)) || (e = dalloc(dd, n))) return e;
   hipStream_t s = ctx->stream;
   int rc = 0;
   if (hipMemcpyAsync(da, a, 4 * n, hipMemcpyHostToDevice, s) != hipSuccess ||
@@ -318,7 +300,6 @@ int klsh_fp_selftest(klsh_ctx* ctx, const float* a, const float* b, uint64_t n, 
       rc = fail(KLSH_E_HIP, "selftest");
   }
   (void)hipStreamSynchronize(s);
-  dfree(da); dfree(db); dfree(ds); dfree(dd);
   return rc;
 }
 

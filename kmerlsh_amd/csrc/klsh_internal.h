@@ -198,6 +198,11 @@ constexpr int kMergeStreams = 3;
 // workgroups stride over a list or an index range on their own; a kernel whose workgroups take
 // one tile each, or wait for one another, must keep its grid.
 inline uint32_t cap_grid(uint32_t g, uint32_t cap) { return cap && g > cap ? cap : g; }
+// the grid of a kernel that strides over n items with 256 lanes: at most `most` workgroups
+inline uint32_t stride_grid(uint64_t n, uint32_t grid_cap, uint64_t most = 16384) {
+  const uint64_t g = (n + 255) / 256;
+  return cap_grid((uint32_t)(g < most ? (g ? g : 1) : most), grid_cap);
+}
 constexpr uint32_t kLongRows = 4096;  // the longest run k_merge_long walks (longer: k_merge_huge)
 inline bool long_ok(int d) { return d == 16 || d == 32; }
 // (2^22 since round 5: with the small-run screen and the big-run prescreen inside it, the one
@@ -488,8 +493,9 @@ void merge_prof_dump(FILE* f);
 // a[i] = min(a[i], b[i])
 void launch_min_u32(uint32_t* a, const uint32_t* b, size_t n, hipStream_t s);
 
-// ---- mode E (klsh_extract.hip): differential k-mer sets and the per-read k-mer vote ----------
-// tab: `mask + 1` (a power of two) 64-bit slots, all ones = empty; kmers[i] == all ones skipped.
+// ---- modes E, B, K: every table below is the k-mer table of klsh_kmer.h (`mask + 1` 64-bit slots,
+// all ones = empty); every launch takes option "grid_cap" last ---------------------------------
+// mode E (klsh_extract.hip): kmers[i] into the set's table (all ones skipped)
 void launch_kset_insert(const uint64_t* kmers, uint64_t n, uint64_t* tab, uint64_t mask,
                         hipStream_t s, uint32_t grid_cap = 0);
 // Read r = seq[off[r] .. off[r+1]): hits[r] = its k-mer positions whose canonical k-mer is in the
@@ -498,7 +504,7 @@ void launch_check_reads(const uint8_t* seq, const uint64_t* off, uint64_t n, int
                         const uint64_t* tab, uint64_t mask, uint32_t* hits, uint8_t* flags,
                         hipStream_t s, uint32_t grid_cap = 0);
 
-// ---- mode B (klsh_kmc.hip): the k-mer table of KMC databases ---------------------------------
+// mode B (klsh_kmc.hip): the k-mer table of KMC databases
 struct KmcParams {
   int k, p;                   // k-mer length, LUT prefix symbols
   uint32_t sufix_size;        // (k - p) / 4 bytes per record
@@ -521,12 +527,21 @@ void launch_kmc_count(const uint64_t* rep, const uint32_t* cnt, uint64_t n, cons
 // occupied slots -> (low word of their first-appearance ordinal, slot), *n_out of them
 void launch_kmc_collect(const uint64_t* tab, const uint64_t* first, uint64_t cap, uint32_t* lo,
                         uint32_t* slot, uint32_t* n_out, hipStream_t s, uint32_t grid_cap = 0);
-void launch_kmc_hi(const uint64_t* first, const uint32_t* slots, uint64_t n, uint32_t* hi,
-                   hipStream_t s, uint32_t grid_cap = 0);
-void launch_kmc_emit_keys(const uint64_t* tab, const uint32_t* order, uint64_t n, uint64_t* out,
-                          hipStream_t s, uint32_t grid_cap = 0);
+// out[i] = src[idx[i]], or hi[i] = its high word
+void launch_ktab_gather(const uint64_t* src, const uint32_t* idx, uint64_t n, uint64_t* out,
+                        hipStream_t s, uint32_t grid_cap = 0);
+void launch_ktab_gather(const uint64_t* src, const uint32_t* idx, uint64_t n, uint32_t* hi,
+                        hipStream_t s, uint32_t grid_cap = 0);
 void launch_kmc_emit(const uint32_t* acc, const uint32_t* order, uint64_t n, uint16_t* out,
                      hipStream_t s, uint32_t grid_cap = 0);
+// The n collected slots in stable ascending order of word[slot], a word of `bits` bits (1..64)
+// whose low halves are in lo (modes B and K, klsh_kmc.cpp): a radix sort over min(bits, 32) bits,
+// then, if the word has high bits, their gather into the free key buffer and a sort over
+// bits - 32.  (lo, slots) and (lo2, slots2) ping-pong, ws: sort_ws_words(n) words; *order = the
+// slot buffer that holds the result.  Returns whether the high pass ran.
+bool order_slots_u64(uint32_t* lo, uint32_t* slots, uint32_t* lo2, uint32_t* slots2, uint32_t n,
+                     int bits, uint32_t* ws, const uint64_t* word, hipStream_t s, uint32_t grid_cap,
+                     uint32_t** order);
 
 // klsh_build_khtable's test hooks and what its last call on the context reached (options
 // "kmc_chunk_records", "kmc_ordinal_base", "kmc_keep_first"; read-only "kmc_decode_launches",
@@ -567,10 +582,10 @@ class KhSource {
 int khtable_run(klsh_ctx* ctx, KhSource& src, int n_samples, int k, const char* out_dir,
                 klsh_khtable_stats* st);
 
-// ---- mode K (klsh_kcount.hip): counting a sample's canonical k-mers -------------------------
+// mode K (klsh_kcount.hip): counting a sample's canonical k-mers
 constexpr uint32_t kKcountWindow = 2048;  // k-mer positions per LDS window (per wave)
-// reads seq[off[r] .. off[r+1]) counted into the table (keys: mask + 1 slots, all ones = empty;
-// cnt: their occurrence counts); ctr[0] += slots claimed, ctr[1] += valid k-mer windows
+// reads seq[off[r] .. off[r+1]) counted into the table (cnt: the slots' occurrence counts);
+// ctr[0] += slots claimed, ctr[1] += valid k-mer windows
 void launch_kcount_reads(const uint8_t* seq, const uint64_t* off, uint64_t n, int k, uint64_t* keys,
                          uint32_t* cnt, uint64_t mask, uint64_t* ctr, hipStream_t s,
                          uint32_t grid_cap = 0);
@@ -581,8 +596,6 @@ void launch_kcount_rehash(const uint64_t* okeys, const uint32_t* ocnt, uint64_t 
 void launch_kcount_collect(const uint64_t* keys, const uint32_t* cnt, uint64_t cap,
                            uint32_t count_min, uint32_t* lo, uint32_t* slot, uint32_t* n_out,
                            hipStream_t s, uint32_t grid_cap = 0);
-void launch_kcount_hi(const uint64_t* keys, const uint32_t* slots, uint64_t n, uint32_t* hi,
-                      hipStream_t s, uint32_t grid_cap = 0);
 // the listing in `order`: KMC value, canonical Kmer image, min(count, 65535)
 void launch_kcount_emit(const uint64_t* keys, const uint32_t* cnt, const uint32_t* order, uint64_t n,
                         int k, uint64_t* val, uint64_t* rep, uint32_t* out_cnt, hipStream_t s,

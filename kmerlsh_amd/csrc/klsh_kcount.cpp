@@ -28,26 +28,23 @@
 
 namespace {
 
+using klsh::DevBuf;
+using klsh::PinBuf;
+
 constexpr uint64_t kBatchReads = 1ull << 18, kTableSlots = 1ull << 22;
 
 // One sample's listing on the device, and its coverage (the float running sum of
 // log((double)count) in listing order, kmer/kmc_reader.cc:143).
 struct Listing {
   uint64_t n = 0;
-  uint64_t* rep = nullptr;
-  uint32_t* cnt = nullptr;
+  DevBuf<uint64_t> rep;
+  DevBuf<uint32_t> cnt;
   float coverage = 0.0f;
 };
 
 class ListingSource : public klsh::KhSource {
  public:
   std::vector<Listing> ls;
-  ~ListingSource() override {
-    for (auto& l : ls) {
-      if (l.rep) (void)hipFree(l.rep);
-      if (l.cnt) (void)hipFree(l.cnt);
-    }
-  }
   uint64_t total(int j) const override { return ls[j].n; }
   uint64_t chunk(int j) const override { return ls[j].n ? ls[j].n : 1; }
   int begin(int, int, hipStream_t) override { return KLSH_OK; }
@@ -86,20 +83,12 @@ class DbWriter {
   DbWriter(klsh_ctx* ctx, int k, uint32_t count_min, klsh_kmcdb_stats& st)
       : hooks_(ctx->kcount), s_(ctx->stream), k_(k), count_min_(count_min),
         st_(st) {}
-  ~DbWriter() {
-    (void)hipStreamSynchronize(s_);  // no copy into the pinned buffers stays queued
-    if (dev_) (void)hipFree(dev_);
-    for (auto& b : buf_) {
-      if (b.host) (void)hipHostFree(b.host);
-      for (hipEvent_t e : {b.e0, b.e1, b.done})
-        if (e) (void)hipEventDestroy(e);
-    }
-  }
+  ~DbWriter() { (void)hipStreamSynchronize(s_); }  // no copy into the pinned buffers stays queued
   int init() {
     for (auto& b : buf_) {
-      KLSH_HIP(hipEventCreate(&b.e0));
-      KLSH_HIP(hipEventCreate(&b.e1));
-      KLSH_HIP(hipEventCreate(&b.done));
+      KLSH_HIP(b.e0.create());
+      KLSH_HIP(b.e1.create());
+      KLSH_HIP(b.done.create());
     }
     return KLSH_OK;
   }
@@ -136,30 +125,26 @@ class DbWriter {
 
  private:
   struct Buf {
-    uint8_t* host = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr, done = nullptr;  // around the kernel; after the copy
+    PinBuf<uint8_t> host;
+    klsh::Event e0, e1, done;  // around the kernel; after the copy
   } buf_[2];
   klsh::KcountHooks& hooks_;
   hipStream_t s_;
   int k_;
   uint32_t count_min_;
   klsh_kmcdb_stats& st_;
-  uint8_t* dev_ = nullptr;
+  DevBuf<uint8_t> dev_;
   uint64_t cap_ = 0;  // bytes of dev_ and of each pinned buffer
   static constexpr uint64_t kChunkRecords = 1ull << 22, kMinBytes = 4ull << 20;
 
   int reserve(uint64_t bytes) {
     if (bytes <= cap_) return KLSH_OK;
     KLSH_HIP(hipStreamSynchronize(s_));
-    if (dev_) (void)hipFree(dev_);
-    dev_ = nullptr;
     cap_ = 0;
-    for (auto& b : buf_) {
-      if (b.host) (void)hipHostFree(b.host);
-      b.host = nullptr;
-    }
-    KLSH_HIP(hipMalloc((void**)&dev_, bytes));
-    for (auto& b : buf_) KLSH_HIP(hipHostMalloc((void**)&b.host, bytes, hipHostMallocDefault));
+    dev_.reset();
+    for (auto& b : buf_) b.host.reset();
+    KLSH_HIP(dev_.alloc(bytes));
+    for (auto& b : buf_) KLSH_HIP(b.host.alloc(bytes));
     cap_ = bytes;
     return KLSH_OK;
   }
@@ -220,7 +205,7 @@ class DbWriter {
       Buf& b = buf_[(q0 / per) & 1];
       const uint64_t mq = std::min<uint64_t>(per, entries - q0);
       KLSH_HIP(hipEventRecord(b.e0, s_));
-      klsh::launch_kmcdb_lut(val, n, q0, mq, k_, p, reinterpret_cast<uint64_t*>(dev_), s_,
+      klsh::launch_kmcdb_lut(val, n, q0, mq, k_, p, reinterpret_cast<uint64_t*>(dev_.get()), s_,
                              hooks_.grid_cap);
       KLSH_HIP(hipGetLastError());
       KLSH_HIP(hipEventRecord(b.e1, s_));
@@ -249,30 +234,15 @@ class Counter {
   Counter(klsh_ctx* ctx, int k, uint32_t count_min, klsh_kcount_stats& st)
       : hooks_(ctx->kcount), s_(ctx->stream), k_(k), count_min_(count_min),
         st_(st) {}
-  ~Counter() {
-    for (auto& sl : slot_) {
-      if (sl.dseq) (void)hipFree(sl.dseq);
-      if (sl.doff) (void)hipFree(sl.doff);
-      if (sl.e0) (void)hipEventDestroy(sl.e0);
-      if (sl.e1) (void)hipEventDestroy(sl.e1);
-    }
-    for (void* p : {(void*)keys_, (void*)cnt_, (void*)ctr_, (void*)lo_, (void*)lo2_, (void*)sl_,
-                    (void*)sl2_, (void*)ws_, (void*)val_})
-      if (p) (void)hipFree(p);
-    if (hctr_) (void)hipHostFree(hctr_);
-  }
-
   int init() {
     cap_ = hooks_.table_slots ? hooks_.table_slots : kTableSlots;
     hooks_.peak_slots = cap_;
-    KLSH_HIP(hipMalloc((void**)&keys_, cap_ * 8));
-    KLSH_HIP(hipMalloc((void**)&cnt_, cap_ * 4));
-    KLSH_HIP(hipMalloc((void**)&ctr_, 64));
-    KLSH_HIP(hipHostMalloc((void**)&hctr_, 64, hipHostMallocDefault));
-    for (auto& sl : slot_) {
-      KLSH_HIP(hipEventCreate(&sl.e0));
-      KLSH_HIP(hipEventCreate(&sl.e1));
-    }
+    KLSH_HIP(keys_.alloc(cap_));
+    KLSH_HIP(cnt_.alloc(cap_));
+    KLSH_HIP(ctr_.alloc(8));
+    KLSH_HIP(hctr_.alloc(8));
+    for (auto& sl : slot_)
+      if (int rc = sl.dev.init()) return rc;
     return KLSH_OK;
   }
 
@@ -294,10 +264,7 @@ class Counter {
   struct Slot {
     std::vector<char> seq;
     std::vector<uint64_t> off;
-    uint8_t* dseq = nullptr;
-    uint64_t* doff = nullptr;
-    uint64_t cap_b = 0, cap_r = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    klsh::ReadBatch dev;
   } slot_[2];
   klsh::KcountHooks& hooks_;
   hipStream_t s_;
@@ -305,9 +272,9 @@ class Counter {
   uint32_t count_min_;
   klsh_kcount_stats& st_;
   uint64_t cap_ = 0, occ_ = 0, pos_ = 0;
-  uint64_t *keys_ = nullptr, *ctr_ = nullptr, *hctr_ = nullptr, *val_ = nullptr;
-  uint32_t *cnt_ = nullptr, *lo_ = nullptr, *lo2_ = nullptr, *sl_ = nullptr, *sl2_ = nullptr,
-           *ws_ = nullptr;
+  PinBuf<uint64_t> hctr_;
+  DevBuf<uint64_t> keys_, ctr_, val_;
+  DevBuf<uint32_t> cnt_, lo_, lo2_, sl_, sl2_, ws_;
   uint64_t sort_cap_ = 0;
 
   // the table doubled until `more` further k-mers keep it at most half full
@@ -315,13 +282,10 @@ class Counter {
     while (occ_ + more > cap_ / 2) {
       const uint64_t ncap = cap_ * 2;
       if (ncap > (1ull << 32)) return set_error(KLSH_E_RANGE, "more than 2^31 distinct k-mers in a sample");
-      uint64_t* nkeys = nullptr;
-      uint32_t* ncnt = nullptr;
-      if (hipMalloc((void**)&nkeys, ncap * 8) != hipSuccess ||
-          hipMalloc((void**)&ncnt, ncap * 4) != hipSuccess) {
-        if (nkeys) (void)hipFree(nkeys);
+      DevBuf<uint64_t> nkeys;
+      DevBuf<uint32_t> ncnt;
+      if (nkeys.alloc(ncap) != hipSuccess || ncnt.alloc(ncap) != hipSuccess)
         return set_error(KLSH_E_NOMEM, "count_khtable: the grown k-mer table");
-      }
       hipError_t e = hipMemsetAsync(nkeys, 0xFF, ncap * 8, s_);
       if (e == hipSuccess) e = hipMemsetAsync(ncnt, 0, ncap * 4, s_);
       if (e == hipSuccess) {
@@ -330,15 +294,10 @@ class Counter {
         e = hipGetLastError();
       }
       if (e == hipSuccess) e = hipStreamSynchronize(s_);
-      if (e != hipSuccess) {
-        (void)hipFree(nkeys);
-        (void)hipFree(ncnt);
+      if (e != hipSuccess)
         return set_error(KLSH_E_HIP, (std::string("count_khtable: rehash -> ") + hipGetErrorString(e)).c_str());
-      }
-      (void)hipFree(keys_);
-      (void)hipFree(cnt_);
-      keys_ = nkeys;
-      cnt_ = ncnt;
+      keys_ = std::move(nkeys);  // (the old table is freed)
+      cnt_ = std::move(ncnt);
       cap_ = ncap;
       hooks_.peak_slots = cap_;
       hooks_.rehashes += 1;
@@ -349,27 +308,12 @@ class Counter {
 
   int launch(Slot& sl) {
     const uint64_t n = sl.off.size() - 1, nb = sl.seq.size();
-    if (nb + 64 > sl.cap_b) {
-      if (sl.dseq) (void)hipFree(sl.dseq);
-      sl.dseq = nullptr;
-      sl.cap_b = 0;
-      KLSH_HIP(hipMalloc((void**)&sl.dseq, nb + nb / 4 + 64));
-      sl.cap_b = nb + nb / 4 + 64;
-    }
-    if (n + 1 > sl.cap_r) {
-      if (sl.doff) (void)hipFree(sl.doff);
-      sl.doff = nullptr;
-      sl.cap_r = 0;
-      KLSH_HIP(hipMalloc((void**)&sl.doff, (n + 1) * 8));
-      sl.cap_r = n + 1;
-    }
-    if (nb) KLSH_HIP(hipMemcpyAsync(sl.dseq, sl.seq.data(), nb, hipMemcpyHostToDevice, s_));
-    KLSH_HIP(hipMemcpyAsync(sl.doff, sl.off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s_));
-    KLSH_HIP(hipEventRecord(sl.e0, s_));
-    klsh::launch_kcount_reads(sl.dseq, sl.doff, n, k_, keys_, cnt_, cap_ - 1, ctr_, s_,
+    if (int rc = sl.dev.upload(sl.seq.data(), nb, sl.off.data(), n, nb + nb / 4 + 64, s_)) return rc;
+    KLSH_HIP(hipEventRecord(sl.dev.e0, s_));
+    klsh::launch_kcount_reads(sl.dev.seq, sl.dev.off, n, k_, keys_, cnt_, cap_ - 1, ctr_, s_,
                               hooks_.grid_cap);
     KLSH_HIP(hipGetLastError());
-    KLSH_HIP(hipEventRecord(sl.e1, s_));
+    KLSH_HIP(hipEventRecord(sl.dev.e1, s_));
     KLSH_HIP(hipMemcpyAsync(hctr_, ctr_, 16, hipMemcpyDeviceToHost, s_));
     return KLSH_OK;
   }
@@ -378,7 +322,7 @@ class Counter {
   int finish(Slot& sl) {
     KLSH_HIP(hipStreamSynchronize(s_));
     float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, sl.e0, sl.e1);
+    (void)hipEventElapsedTime(&ms, sl.dev.e0, sl.dev.e1);
     st_.kernel_ms += ms;
     occ_ = hctr_[0];
     pos_ = hctr_[1];
@@ -435,18 +379,13 @@ class Counter {
     st_.positions += pos_;
     st_.distinct += occ_;
     if (occ_ + 64 > sort_cap_) {
-      for (void* p : {(void*)lo_, (void*)lo2_, (void*)sl_, (void*)sl2_, (void*)ws_, (void*)val_})
-        if (p) (void)hipFree(p);
-      lo_ = lo2_ = sl_ = sl2_ = ws_ = nullptr;
-      val_ = nullptr;
       sort_cap_ = 0;
+      for (auto* b : {&lo_, &lo2_, &sl_, &sl2_, &ws_}) b->reset();
+      val_.reset();
       const uint64_t c = occ_ + occ_ / 4 + 64;
-      KLSH_HIP(hipMalloc((void**)&lo_, c * 4));
-      KLSH_HIP(hipMalloc((void**)&lo2_, c * 4));
-      KLSH_HIP(hipMalloc((void**)&sl_, c * 4));
-      KLSH_HIP(hipMalloc((void**)&sl2_, c * 4));
-      KLSH_HIP(hipMalloc((void**)&ws_, klsh::sort_ws_words(c) * 4));
-      KLSH_HIP(hipMalloc((void**)&val_, c * 8));
+      for (auto* b : {&lo_, &lo2_, &sl_, &sl2_}) KLSH_HIP(b->alloc(c));
+      KLSH_HIP(ws_.alloc(klsh::sort_ws_words(c)));
+      KLSH_HIP(val_.alloc(c));
       sort_cap_ = c;
     }
     uint32_t* nout = reinterpret_cast<uint32_t*>(ctr_ + 4);
@@ -457,22 +396,12 @@ class Counter {
     KLSH_HIP(hipGetLastError());
     KLSH_HIP(hipMemcpyAsync(&n, nout, 4, hipMemcpyDeviceToHost, s_));
     KLSH_HIP(hipStreamSynchronize(s_));
-    // ascending KMC value: two stable 32-bit radix sorts, low word then high word
-    uint32_t *ok = lo_, *ov = sl_;
-    if (n) klsh::radix_sort(lo_, sl_, lo2_, sl2_, n, k_ < 16 ? 2 * k_ : 32, ws_, &ok, &ov, s_);
-    if (n && k_ > 16) {
-      uint32_t* hk = ok == lo_ ? lo2_ : lo_;  // the free key buffer
-      uint32_t* hv = ov == sl_ ? sl2_ : sl_;
-      klsh::launch_kcount_hi(keys_, ov, n, hk, s_,
-                             hooks_.grid_cap);
-      uint32_t *ok2 = nullptr, *ov2 = nullptr;
-      klsh::radix_sort(hk, ov, ok, hv, n, 2 * k_ - 32, ws_, &ok2, &ov2, s_);
-      ov = ov2;
-    }
+    uint32_t* ov = nullptr;  // ascending KMC value, a word of 2k bits
+    klsh::order_slots_u64(lo_, sl_, lo2_, sl2_, n, 2 * k_, ws_, keys_, s_, hooks_.grid_cap, &ov);
     KLSH_HIP(hipGetLastError());
     out->n = n;
-    KLSH_HIP(hipMalloc((void**)&out->rep, (uint64_t)(n ? n : 1) * 8));
-    KLSH_HIP(hipMalloc((void**)&out->cnt, (uint64_t)(n ? n : 1) * 4));
+    KLSH_HIP(out->rep.alloc(n));
+    KLSH_HIP(out->cnt.alloc(n));
     klsh::launch_kcount_emit(keys_, cnt_, ov, n, k_, val_, out->rep, out->cnt, s_,
                              hooks_.grid_cap);
     KLSH_HIP(hipGetLastError());
@@ -587,10 +516,8 @@ int count_run(klsh_ctx* ctx, const char* const* fastq_paths, const char* const* 
                             hooks.keep_listing ? &hooks.counts[j] : nullptr);
         if (rc == KLSH_OK && db_names) rc = writer.write(db_names[j], counter.values(), l.cnt, l.n);
         if (!table) {  // nothing reads the listing again
-          if (l.rep) (void)hipFree(l.rep);
-          if (l.cnt) (void)hipFree(l.cnt);
-          l.rep = nullptr;
-          l.cnt = nullptr;
+          l.rep.reset();
+          l.cnt.reset();
         }
       }
     }  // the sample table is freed before the union's

@@ -8,12 +8,10 @@
 //   k_kcount_reads    one wave per read: the read's base codes staged in LDS in windows (one byte
 //                     each, 4 = break), one lane per k-mer position building its value from LDS;
 //                     equal keys of neighbouring lanes (a homopolymer or short-period run) are
-//                     combined, and the first lane of a run probes the table (open addressing,
-//                     64-bit CAS on the key; all ones = empty, never canonical: the all-T k-mer's
-//                     reverse complement is 0) and adds the run's length to the slot's 32-bit count
+//                     combined, and the first lane of a run probes the k-mer table (klsh_kmer.h)
+//                     and adds the run's length to the slot's 32-bit count
 //   k_kcount_rehash   keys and counts into a table of twice the slots (between batches)
-//   k_kcount_collect  slots with count >= count_min -> (low word of the value, slot)
-//   k_kcount_hi       the values' high words, for the second sort pass (k > 16)
+//   k_ktab_collect<ByValue>  slots with count >= count_min -> (low word of the value, slot)
 //   k_kcount_emit     the listing in sorted order: value, rep image, min(count, 65535)
 //   k_kmcdb_pack      a chunk of the listing as the records of a KMC1-layout .kmc_suf
 //   k_kmcdb_lut       the .kmc_pre prefix table: per prefix, the records below it (binary search)
@@ -35,40 +33,11 @@
 
 namespace klsh {
 
-constexpr uint64_t kKcEmpty = ~0ull;
 constexpr int kKcWaves = 4;  // waves per workgroup, each on its own reads
-
-__device__ __forceinline__ uint64_t kc_hash(uint64_t k) {  // murmur3 finalizer
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return k;
-}
 
 __device__ __forceinline__ uint32_t kc_code(uint32_t c) {
   c |= 0x20u;  // the lower-case letter; no other character maps onto a, c, g, t
   return c == 'a' ? 0u : c == 'c' ? 1u : c == 'g' ? 2u : c == 't' ? 3u : 4u;
-}
-
-// the slot of `key`, claimed if absent (*fresh = 1 then)
-__device__ __forceinline__ uint64_t kc_slot(unsigned long long* keys, uint64_t mask, uint64_t key,
-                                            uint32_t* fresh) {
-  uint64_t h = kc_hash(key) & mask;
-  while (true) {
-    // a key never changes once set: a read of it settles the probe without an atomic
-    unsigned long long t = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t == kKcEmpty) {
-      t = atomicCAS(&keys[h], (unsigned long long)kKcEmpty, (unsigned long long)key);
-      if (t == kKcEmpty) {
-        *fresh = 1u;
-        return h;
-      }
-    }
-    if (t == key) return h;
-    h = (h + 1) & mask;
-  }
 }
 
 // ctr[0] += slots claimed, ctr[1] += valid k-mer windows (one add per wave and counter)
@@ -104,7 +73,7 @@ __global__ __launch_bounds__(256) void k_kcount_reads(const uint8_t* __restrict_
             v = (v << 2) | (uint64_t)(c & 3u);
           }
         const bool valid = brk < 4u;
-        const uint64_t key = valid ? kmc_canonical(v, k) : kKcEmpty;
+        const uint64_t key = valid ? kmc_canonical(v, k) : kKtabEmpty;
         // runs of equal keys in neighbouring lanes: the first lane adds the run's length
         const uint64_t prev = __shfl_up((unsigned long long)key, 1, 64);
         const bool head = valid && (lane == 0u || key != prev);
@@ -114,7 +83,7 @@ __global__ __launch_bounds__(256) void k_kcount_reads(const uint8_t* __restrict_
           const uint64_t stop = (hm | ~vm) & ~((2ull << lane) - 1ull);  // next head or break above
           const uint32_t run = (stop ? (uint32_t)__builtin_ctzll(stop) : 64u) - lane;
           uint32_t fresh = 0;
-          const uint64_t h = kc_slot(keys, mask, key, &fresh);
+          const uint64_t h = ktab_claim_read(keys, mask, key, &fresh);
           n_new += fresh;
           if (__hip_atomic_load(&cnt[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 65535u)
             atomicAdd(&cnt[h], run);
@@ -139,44 +108,20 @@ __global__ __launch_bounds__(256) void k_kcount_rehash(const uint64_t* __restric
                                                        uint32_t* __restrict__ cnt, uint64_t mask) {
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < ocap; i += (uint64_t)gridDim.x * 256ull) {
     const uint64_t key = okeys[i];
-    if (key == kKcEmpty) continue;
+    if (key == kKtabEmpty) continue;
     uint32_t fresh = 0;
-    const uint64_t h = kc_slot(keys, mask, key, &fresh);
+    const uint64_t h = ktab_claim_read(keys, mask, key, &fresh);
     cnt[h] = ocnt[i];  // the old table holds a key once
   }
 }
 
-__global__ __launch_bounds__(256) void k_kcount_collect(const uint64_t* __restrict__ keys,
-                                                        const uint32_t* __restrict__ cnt,
-                                                        uint64_t cap, uint32_t count_min,
-                                                        uint32_t* __restrict__ lo,
-                                                        uint32_t* __restrict__ slot,
-                                                        uint32_t* __restrict__ n_out) {
-  // cap is a power of two >= 1024: every wave's 64 lanes are in or out of range together
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull;
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * 256ull) {
-    const uint64_t key = keys[i];
-    const bool take = key != kKcEmpty && cnt[i] >= count_min;
-    const uint64_t m = __ballot(take);
-    if (!m) continue;
-    uint32_t base = 0;  // one add per wave, not per entry (a single counter)
-    if (lane == (uint32_t)__builtin_ctzll(m)) base = atomicAdd(n_out, (uint32_t)__popcll(m));
-    base = __shfl(base, (int)__builtin_ctzll(m), 64);
-    if (take) {
-      const uint32_t o = base + (uint32_t)__popcll(m & below);
-      lo[o] = (uint32_t)key;
-      slot[o] = (uint32_t)i;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void k_kcount_hi(const uint64_t* __restrict__ keys,
-                                                   const uint32_t* __restrict__ slots, uint64_t n,
-                                                   uint32_t* __restrict__ hi) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull)
-    hi[i] = (uint32_t)(keys[slots[i]] >> 32);
-}
+// k_ktab_collect's selection of mode K: the slots counted count_min times at least, by KMC value
+struct ByValue {
+  const uint32_t* cnt;
+  uint32_t count_min;
+  __device__ bool take(uint64_t i) const { return cnt[i] >= count_min; }
+  __device__ uint32_t low(uint64_t, uint64_t key) const { return (uint32_t)key; }
+};
 
 __global__ __launch_bounds__(256) void k_kcount_emit(const uint64_t* __restrict__ keys,
                                                      const uint32_t* __restrict__ cnt,
@@ -247,11 +192,6 @@ __global__ __launch_bounds__(256) void k_kmcdb_lut(const uint64_t* __restrict__ 
   }
 }
 
-static uint32_t kc_grid(uint64_t n, uint32_t grid_cap) {
-  const uint64_t g = (n + 255) / 256;
-  return cap_grid((uint32_t)(g < 16384 ? (g ? g : 1) : 16384), grid_cap);
-}
-
 void launch_kcount_reads(const uint8_t* seq, const uint64_t* off, uint64_t n, int k, uint64_t* keys,
                          uint32_t* cnt, uint64_t mask, uint64_t* ctr, hipStream_t s,
                          uint32_t grid_cap) {
@@ -264,34 +204,30 @@ void launch_kcount_reads(const uint8_t* seq, const uint64_t* off, uint64_t n, in
 }
 void launch_kcount_rehash(const uint64_t* okeys, const uint32_t* ocnt, uint64_t ocap, uint64_t* keys,
                           uint32_t* cnt, uint64_t mask, hipStream_t s, uint32_t grid_cap) {
-  k_kcount_rehash<<<kc_grid(ocap, grid_cap), 256, 0, s>>>(okeys, ocnt, ocap,
+  k_kcount_rehash<<<stride_grid(ocap, grid_cap), 256, 0, s>>>(okeys, ocnt, ocap,
                                                           reinterpret_cast<unsigned long long*>(keys),
                                                           cnt, mask);
 }
 void launch_kcount_collect(const uint64_t* keys, const uint32_t* cnt, uint64_t cap,
                            uint32_t count_min, uint32_t* lo, uint32_t* slot, uint32_t* n_out,
                            hipStream_t s, uint32_t grid_cap) {
-  k_kcount_collect<<<kc_grid(cap, grid_cap), 256, 0, s>>>(keys, cnt, cap, count_min, lo, slot,
-                                                          n_out);
-}
-void launch_kcount_hi(const uint64_t* keys, const uint32_t* slots, uint64_t n, uint32_t* hi,
-                      hipStream_t s, uint32_t grid_cap) {
-  if (n) k_kcount_hi<<<kc_grid(n, grid_cap), 256, 0, s>>>(keys, slots, n, hi);
+  k_ktab_collect<<<stride_grid(cap, grid_cap), 256, 0, s>>>(keys, ByValue{cnt, count_min}, cap, lo,
+                                                            slot, n_out);
 }
 void launch_kcount_emit(const uint64_t* keys, const uint32_t* cnt, const uint32_t* order, uint64_t n,
                         int k, uint64_t* val, uint64_t* rep, uint32_t* out_cnt, hipStream_t s,
                         uint32_t grid_cap) {
   if (n)
-    k_kcount_emit<<<kc_grid(n, grid_cap), 256, 0, s>>>(keys, cnt, order, n, k, val, rep, out_cnt);
+    k_kcount_emit<<<stride_grid(n, grid_cap), 256, 0, s>>>(keys, cnt, order, n, k, val, rep, out_cnt);
 }
 void launch_kmcdb_pack(const uint64_t* val, const uint32_t* cnt, uint64_t r0, uint64_t m,
                        uint32_t sufix_size, uint8_t* out, hipStream_t s, uint32_t grid_cap) {
-  if (m) k_kmcdb_pack<<<kc_grid(m, grid_cap), 256, 0, s>>>(val, cnt, r0, m, sufix_size, out);
+  if (m) k_kmcdb_pack<<<stride_grid(m, grid_cap), 256, 0, s>>>(val, cnt, r0, m, sufix_size, out);
 }
 void launch_kmcdb_lut(const uint64_t* val, uint64_t n, uint64_t q0, uint64_t mq, int k, int p,
                       uint64_t* lut, hipStream_t s, uint32_t grid_cap) {
   if (mq)
-    k_kmcdb_lut<<<kc_grid(mq, grid_cap), 256, 0, s>>>(val, n, q0, mq, (uint32_t)(2 * (k - p)), lut);
+    k_kmcdb_lut<<<stride_grid(mq, grid_cap), 256, 0, s>>>(val, n, q0, mq, (uint32_t)(2 * (k - p)), lut);
 }
 
 }  // namespace klsh

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "klsh_ctx.h"
+#include "klsh_kmer.h"
 
 namespace {
 
@@ -132,15 +133,7 @@ struct KmcDb {
 // 0x9368e53c2f6af274 / 0x586dcd208f7cd3fd).  k_bytes <= 8, so the input is one tail block: the
 // image's low k_bytes bytes (the Kmer's bytes in memory order, little-endian) as k1, k2 = 0.
 inline uint64_t rotl64(uint64_t v, int r) { return (v << r) | (v >> (64 - r)); }
-inline uint64_t fmix64(uint64_t k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return k;
-}
-uint64_t kmer_hash(uint64_t image, int nbytes) {
+uint64_t ref_kmer_hash(uint64_t image, int nbytes) {
   uint64_t h1 = 0x9368e53c2f6af274ull, h2 = 0x586dcd208f7cd3fdull;
   const uint64_t c1 = 0x87c37b91114253d5ull, c2 = 0x4cf5ad432745937full;
   uint64_t k1 = nbytes >= 8 ? image : (image & ((1ull << (8 * nbytes)) - 1ull));
@@ -158,8 +151,8 @@ uint64_t kmer_hash(uint64_t image, int nbytes) {
   h2 ^= (uint64_t)nbytes;
   h1 += h2;
   h2 += h1;
-  h1 = fmix64(h1);
-  h2 = fmix64(h2);
+  h1 = klsh::kmer_hash(h1);  // fmix64, the finalizer the device tables hash with too
+  h2 = klsh::kmer_hash(h2);
   return h1 + h2;
 }
 
@@ -309,7 +302,7 @@ extern "C" int klsh_cuckoo_order(const uint64_t* images, uint64_t n, int k, uint
   if (k < 1 || k > 32) return set_error(KLSH_E_RANGE, "k must be in [1, 32]");
   if (n >= 0xFFFFFFFFull) return set_error(KLSH_E_RANGE, "too many k-mers");
   std::vector<uint64_t> hv(n);
-  for (uint64_t i = 0; i < n; ++i) hv[i] = kmer_hash(images[i], (k + 3) / 4);
+  for (uint64_t i = 0; i < n; ++i) hv[i] = ref_kmer_hash(images[i], (k + 3) / 4);
   CuckooOrder t(hv, 16);
   for (uint64_t i = 0; i < n; ++i) t.insert((uint32_t)i);
   const std::vector<uint32_t> o = t.order();
@@ -330,17 +323,10 @@ extern "C" int klsh_khtable_first(klsh_ctx* ctx, uint64_t* images, uint64_t* n) 
   return KLSH_OK;
 }
 
-// KLSH_HIP for khtable_run, which releases its buffers at `done` instead of returning
-#define KLSH_KHIP(call)                      \
-  do {                                       \
-    hipError_t e_ = (call);                  \
-    if (e_ != hipSuccess) {                  \
-      rc = klsh::hip_fail(#call, e_);        \
-      goto done;                             \
-    }                                        \
-  } while (0)
 
 namespace {
+
+using klsh::DevBuf;
 
 // klsh_build_khtable's records: every .kmc_suf streamed in chunks (the files are the I/O) and
 // decoded on the device (k_kmc_decode).
@@ -349,22 +335,17 @@ class KmcFileSource : public klsh::KhSource {
   static constexpr uint64_t kChunkBytes = 64ull << 20;
   KmcFileSource(const std::vector<KmcDb>& dbs, klsh::KmcHooks& hooks, klsh_khtable_stats& st)
       : dbs_(dbs), hooks_(hooks), st_(st), hrec_(kChunkBytes) {}
-  ~KmcFileSource() override {
-    if (f_) fclose(f_);
-    for (void* ptr : {(void*)drec_, (void*)drep_, (void*)dcnt_, (void*)dlut_, (void*)nvalid_})
-      if (ptr) (void)hipFree(ptr);
-  }
   int alloc() {
     uint64_t max_lut = 0, max_chunk_recs = 0;
     for (const auto& db : dbs_) {
       max_lut = std::max<uint64_t>(max_lut, db.lut.size());
       max_chunk_recs = std::max<uint64_t>(max_chunk_recs, kChunkBytes / db.params().rec_size + 1);
     }
-    KLSH_HIP(hipMalloc((void**)&drec_, kChunkBytes + 64));
-    KLSH_HIP(hipMalloc((void**)&drep_, max_chunk_recs * 8));
-    KLSH_HIP(hipMalloc((void**)&dcnt_, max_chunk_recs * 4));
-    KLSH_HIP(hipMalloc((void**)&dlut_, max_lut * 8));
-    KLSH_HIP(hipMalloc((void**)&nvalid_, 64));
+    KLSH_HIP(drec_.alloc(kChunkBytes + 64));
+    KLSH_HIP(drep_.alloc(max_chunk_recs));
+    KLSH_HIP(dcnt_.alloc(max_chunk_recs));
+    KLSH_HIP(dlut_.alloc(max_lut));
+    KLSH_HIP(nvalid_.alloc(16));
     return KLSH_OK;
   }
   uint64_t total(int j) const override { return dbs_[j].total; }
@@ -379,10 +360,10 @@ class KmcFileSource : public klsh::KhSource {
     cov_ = 0.0f;
     KLSH_HIP(hipMemcpyAsync(dlut_, db.lut.data(), db.lut.size() * 8, hipMemcpyHostToDevice, s));
     KLSH_HIP(hipMemsetAsync(nvalid_, 0, 4, s));
-    f_ = fopen(db.suf.c_str(), "rb");
+    f_.reset(fopen(db.suf.c_str(), "rb"));
     if (!f_) return set_error(KLSH_E_ARG, ("cannot open " + db.suf).c_str());
     char mark[4];
-    if (fread(mark, 1, 4, f_) != 4 || memcmp(mark, "KMCS", 4))
+    if (fread(mark, 1, 4, f_.get()) != 4 || memcmp(mark, "KMCS", 4))
       return set_error(KLSH_E_ARG, (db.suf + ": bad marker").c_str());
     return KLSH_OK;
   }
@@ -390,7 +371,7 @@ class KmcFileSource : public klsh::KhSource {
            hipStream_t s) override {
     const KmcDb& db = dbs_[j];
     const double tio = now_ms();
-    if (fread(hrec_.data(), kp_.rec_size, n, f_) != n)
+    if (fread(hrec_.data(), kp_.rec_size, n, f_.get()) != n)
       return set_error(KLSH_E_ARG, (db.suf + ": short file").c_str());
     st_.io_ms += now_ms() - tio;
     KLSH_HIP(hipMemcpyAsync(drec_, hrec_.data(), n * kp_.rec_size, hipMemcpyHostToDevice, s));
@@ -412,8 +393,7 @@ class KmcFileSource : public klsh::KhSource {
     }
   }
   int end(int j, int pass, uint64_t* listed, float* coverage, hipStream_t s) override {
-    fclose(f_);
-    f_ = nullptr;
+    f_.reset();
     st_.records += dbs_[j].total;
     if (pass == 0) {
       uint32_t nv = 0;
@@ -432,175 +412,204 @@ class KmcFileSource : public klsh::KhSource {
   std::vector<uint8_t> hrec_;
   klsh::KmcParams kp_{};
   float cov_ = 0.0f;
-  FILE* f_ = nullptr;
-  uint8_t* drec_ = nullptr;
-  uint64_t *drep_ = nullptr, *dlut_ = nullptr;
-  uint32_t *dcnt_ = nullptr, *nvalid_ = nullptr;
+  klsh::File f_;
+  DevBuf<uint8_t> drec_;
+  DevBuf<uint64_t> drep_, dlut_;
+  DevBuf<uint32_t> dcnt_, nvalid_;
+};
+
+// khtable_run's state and its steps, in the order they run.
+struct KhBuild {
+  klsh::KhSource& src;
+  const int n_samples, k;
+  klsh_khtable_stats& st;
+  klsh::KmcHooks& hooks;
+  const uint32_t gc;  // option "grid_cap" (tests): workgroups per launch, at most
+  const hipStream_t s;
+  uint64_t cap = 1024;               // slots of the union's table
+  DevBuf<uint64_t> tab, first;       // its keys; per slot the smallest ordinal that listed it
+  DevBuf<uint32_t> acc, slots, nvalid;  // a sample's counts per slot; the slots in row order
+  DevBuf<uint16_t> col;
+  uint32_t kmap = 0;                 // distinct k-mers = rows
+  std::vector<uint64_t> base;        // base[j]: sample j's first ordinal
+  std::vector<float> coverage;
+  klsh::File fh, fb, fl;
+
+  KhBuild(klsh_ctx* ctx, klsh::KhSource& src_, int n, int k_, klsh_khtable_stats* st_)
+      : src(src_), n_samples(n), k(k_), st(*st_), hooks(ctx->kmc), gc(ctx->kmc.grid_cap),
+        s(ctx->stream), base(n + 1, ctx->kmc.ordinal_base), coverage(n, 0.0f) {}
+
+  int init() {
+    uint64_t records = 0;
+    for (int j = 0; j < n_samples; ++j) records += src.total(j);
+    while (cap < 2 * (records + (uint64_t)n_samples)) cap <<= 1;
+    if (cap > (1ull << 32)) return set_error(KLSH_E_RANGE, "more than 2^31 distinct k-mers");
+    KLSH_HIP(tab.alloc(cap));
+    KLSH_HIP(first.alloc(cap));
+    KLSH_HIP(acc.alloc(cap));
+    KLSH_HIP(nvalid.alloc(16));
+    KLSH_HIP(hipMemsetAsync(tab, 0xFF, cap * 8, s));
+    KLSH_HIP(hipMemsetAsync(first, 0xFF, cap * 8, s));
+    return KLSH_OK;
+  }
+
+  // sample j's records through the source and the union (pass 0) / the counts (pass 1)
+  int stream(int j, int pass, uint64_t* listed) {
+    const uint64_t total = src.total(j), per_chunk = src.chunk(j);
+    if (int rc = src.begin(j, pass, s)) return rc;
+    for (uint64_t r0 = 0; r0 < total; r0 += per_chunk) {
+      const uint64_t n = std::min<uint64_t>(per_chunk, total - r0);
+      const uint64_t* drep = nullptr;
+      const uint32_t* dcnt = nullptr;
+      if (int rc = src.feed(j, pass, r0, n, &drep, &dcnt, s)) return rc;
+      if (pass == 0) klsh::launch_kmc_union(drep, n, base[j] + r0, tab, first, cap - 1, s, gc);
+      else klsh::launch_kmc_count(drep, dcnt, n, tab, cap - 1, acc, s, gc);
+      KLSH_HIP(hipGetLastError());
+      src.fed(j, pass, n);
+      KLSH_HIP(hipStreamSynchronize(s));  // the source reuses its buffers for the next chunk
+    }
+    return src.end(j, pass, listed, &coverage[j], s);
+  }
+
+  // pass 0: every sample's k-mers into the table, each with its first ordinal
+  int union_pass() {
+    DevBuf<uint64_t> dzero;  // the all-A k-mer of a filtered sample
+    KLSH_HIP(dzero.alloc(8));
+    for (int j = 0; j < n_samples; ++j) {
+      const uint64_t total = src.total(j);
+      uint64_t nv = 0;
+      if (int rc = stream(j, 0, &nv)) return rc;
+      st.records_listed += nv;
+      // fewer listed than the total: KmcRead's vector keeps default (all-A) k-mers at the end
+      if (nv < total) {
+        const uint64_t zero = 0;
+        KLSH_HIP(hipMemcpyAsync(dzero, &zero, 8, hipMemcpyHostToDevice, s));
+        klsh::launch_kmc_union(dzero, 1, base[j] + total, tab, first, cap - 1, s, gc);
+        KLSH_HIP(hipGetLastError());
+        KLSH_HIP(hipStreamSynchronize(s));
+      }
+      base[j + 1] = base[j] + total + 1;
+    }
+    return KLSH_OK;
+  }
+
+  // The rows: the occupied slots in first-appearance order (by their 64-bit ordinal), then in the
+  // order of the reference's libcuckoo table after those inserts; kmer_set.hex written, the other
+  // two files opened.
+  int order_rows(const std::string& dir) {
+    const uint64_t room = cap / 2 + 64;
+    DevBuf<uint32_t> lo, lo2, slots2, ws;
+    KLSH_HIP(lo.alloc(room));
+    KLSH_HIP(lo2.alloc(room));
+    KLSH_HIP(slots.alloc(room));
+    KLSH_HIP(slots2.alloc(room));
+    KLSH_HIP(ws.alloc(klsh::sort_ws_words(room)));
+    KLSH_HIP(hipMemsetAsync(nvalid, 0, 4, s));
+    klsh::launch_kmc_collect(tab, first, cap, lo, slots, nvalid, s, gc);
+    KLSH_HIP(hipGetLastError());
+    KLSH_HIP(hipMemcpyAsync(&kmap, nvalid, 4, hipMemcpyDeviceToHost, s));
+    KLSH_HIP(hipStreamSynchronize(s));
+    int hbits = 0;
+    while (hbits < 32 && (base[n_samples] >> 32) >> hbits) ++hbits;
+    uint32_t* ov = nullptr;
+    if (klsh::order_slots_u64(lo, slots, lo2, slots2, kmap, 32 + hbits, ws, first, s, gc, &ov))
+      hooks.high_sort = 1;
+    KLSH_HIP(hipGetLastError());
+    if (ov != slots) KLSH_HIP(hipMemcpyAsync(slots, ov, kmap * 4ull, hipMemcpyDeviceToDevice, s));
+    DevBuf<uint64_t> keys_out;
+    KLSH_HIP(keys_out.alloc(kmap));
+    KLSH_HIP(col.alloc(kmap));
+    klsh::launch_ktab_gather(tab, slots, kmap, keys_out.get(), s, gc);
+    KLSH_HIP(hipGetLastError());
+    std::vector<uint64_t> hkeys(kmap);
+    std::vector<uint32_t> hslots(kmap);
+    if (kmap) {
+      KLSH_HIP(hipMemcpyAsync(hkeys.data(), keys_out, kmap * 8ull, hipMemcpyDeviceToHost, s));
+      KLSH_HIP(hipMemcpyAsync(hslots.data(), slots, kmap * 4ull, hipMemcpyDeviceToHost, s));
+    }
+    KLSH_HIP(hipStreamSynchronize(s));
+    if (hooks.keep_first) hooks.first = hkeys;
+    {  // the reference's row order: its libcuckoo table after the first-appearance inserts
+      const double tc = now_ms();
+      std::vector<uint64_t> hv(kmap);
+      for (uint32_t i = 0; i < kmap; ++i) hv[i] = ref_kmer_hash(hkeys[i], (k + 3) / 4);
+      CuckooOrder table(hv, 16);
+      for (uint32_t i = 0; i < kmap; ++i) table.insert(i);
+      const std::vector<uint32_t> ord = table.order();
+      std::vector<uint64_t> k2(kmap);
+      std::vector<uint32_t> s2(kmap);
+      for (uint32_t i = 0; i < kmap; ++i) {
+        k2[i] = hkeys[ord[i]];
+        s2[i] = hslots[ord[i]];
+      }
+      hkeys.swap(k2);
+      if (kmap) KLSH_HIP(hipMemcpyAsync(slots, s2.data(), kmap * 4ull, hipMemcpyHostToDevice, s));
+      KLSH_HIP(hipStreamSynchronize(s));
+      st.order_ms = now_ms() - tc;
+    }
+    // kmer_set.hex: the k-mers' 8-byte images in row order (Kmer::writeBytes, kmer/Kmer.cc:307)
+    fh.reset(fopen((dir + "kmer_set.hex").c_str(), "wb"));
+    fb.reset(fopen((dir + "kmer_count.bin").c_str(), "wb"));
+    fl.reset(fopen((dir + "kmer_count.log").c_str(), "w"));
+    if (!fh || !fb || !fl)
+      return set_error(KLSH_E_ARG, "cannot write kmer_set.hex / kmer_count.bin / kmer_count.log");
+    if (kmap && fwrite(hkeys.data(), 8, kmap, fh.get()) != kmap)
+      return set_error(KLSH_E_ARG, "kmer_set.hex: write failed");
+    return KLSH_OK;
+  }
+
+  // pass 1: per sample its summed counts, written as its uint16 column in row order (WriteHT,
+  // io/ioHT.cc:30-55)
+  int count_pass() {
+    for (int j = 0; j < n_samples; ++j) {
+      KLSH_HIP(hipMemsetAsync(acc, 0, cap * 4, s));
+      if (int rc = stream(j, 1, nullptr)) return rc;
+      klsh::launch_kmc_emit(acc, slots, kmap, col, s, gc);
+      KLSH_HIP(hipGetLastError());
+      std::vector<uint16_t> hcol(kmap);
+      if (kmap) KLSH_HIP(hipMemcpyAsync(hcol.data(), col, kmap * 2ull, hipMemcpyDeviceToHost, s));
+      KLSH_HIP(hipStreamSynchronize(s));
+      if (kmap && fwrite(hcol.data(), 2, kmap, fb.get()) != kmap)
+        return set_error(KLSH_E_ARG, "kmer_count.bin: write failed");
+    }
+    return KLSH_OK;
+  }
+
+  // kmer_count.log: "%llu" kmap_size, then "\t%f" per sample coverage (io/ioHT.cc:170-187)
+  int write_log() {
+    fprintf(fl.get(), "%llu", (unsigned long long)kmap);
+    for (int j = 0; j < n_samples; ++j) fprintf(fl.get(), "\t%f", (double)coverage[j]);
+    st.kmap_size = kmap;
+    return KLSH_OK;
+  }
 };
 
 }  // namespace
 
+bool klsh::order_slots_u64(uint32_t* lo, uint32_t* slots, uint32_t* lo2, uint32_t* slots2, uint32_t n,
+                           int bits, uint32_t* ws, const uint64_t* word, hipStream_t s,
+                           uint32_t grid_cap, uint32_t** order) {
+  uint32_t *ok = nullptr, *ov = nullptr;
+  klsh::radix_sort(lo, slots, lo2, slots2, n, std::min(bits, 32), ws, &ok, &ov, s);
+  if (bits > 32) {
+    uint32_t* hk = ok == lo ? lo2 : lo;  // the free key buffer
+    uint32_t* hv = ov == slots ? slots2 : slots;
+    klsh::launch_ktab_gather(word, ov, n, hk, s, grid_cap);
+    klsh::radix_sort(hk, ov, ok, hv, n, bits - 32, ws, &ok, &ov, s);
+  }
+  *order = ov;
+  return bits > 32;
+}
+
 int klsh::khtable_run(klsh_ctx* ctx, klsh::KhSource& src, int n_samples, int k, const char* out_dir,
                       klsh_khtable_stats* st) {
-  klsh_khtable_stats& local = *st;
-  klsh::KmcHooks& hooks = ctx->kmc;
-  const uint32_t gc = hooks.grid_cap;  // option "grid_cap" (tests): workgroups per launch, at most
-  const hipStream_t s = ctx->stream;
   const std::string dir = (out_dir && *out_dir) ? std::string(out_dir) + "/" : std::string();
-  uint64_t records = 0;
-  for (int j = 0; j < n_samples; ++j) records += src.total(j);
-
-  uint64_t cap = 1024;
-  while (cap < 2 * (records + (uint64_t)n_samples)) cap <<= 1;
-  if (cap > (1ull << 32)) return set_error(KLSH_E_RANGE, "more than 2^31 distinct k-mers");
-  const uint64_t mask = cap - 1;
-  int rc = KLSH_OK;
-  uint64_t *tab = nullptr, *first = nullptr, *keys_out = nullptr, *dzero = nullptr;
-  uint32_t *acc = nullptr, *nvalid = nullptr, *lo = nullptr, *lo2 = nullptr;
-  uint32_t *slots = nullptr, *slots2 = nullptr, *ws = nullptr;
-  uint16_t* col = nullptr;
-  std::vector<uint64_t> base(n_samples + 1, hooks.ordinal_base);  // base[j]: sample j's first ordinal
-  uint32_t kmap = 0;
-  FILE *fh = nullptr, *fb = nullptr, *fl = nullptr;
-  std::vector<float> coverage(n_samples, 0.0f);
-  KLSH_KHIP(hipMalloc((void**)&tab, cap * 8));
-  KLSH_KHIP(hipMalloc((void**)&first, cap * 8));
-  KLSH_KHIP(hipMalloc((void**)&acc, cap * 4));
-  KLSH_KHIP(hipMalloc((void**)&nvalid, 64));
-  KLSH_KHIP(hipMalloc((void**)&dzero, 64));  // the all-A k-mer of a filtered sample
-  KLSH_KHIP(hipMemsetAsync(tab, 0xFF, cap * 8, s));
-  KLSH_KHIP(hipMemsetAsync(first, 0xFF, cap * 8, s));
-
-  // Stream sample j's records through the source + the union (pass 0) / the counts (pass 1).
-  for (int pass = 0; pass < 2; ++pass) {
-    for (int j = 0; j < n_samples; ++j) {
-      const uint64_t total = src.total(j), per_chunk = src.chunk(j);
-      if (pass == 1) KLSH_KHIP(hipMemsetAsync(acc, 0, cap * 4, s));
-      if ((rc = src.begin(j, pass, s))) goto done;
-      for (uint64_t r0 = 0; r0 < total; r0 += per_chunk) {
-        const uint64_t n = std::min<uint64_t>(per_chunk, total - r0);
-        const uint64_t* drep = nullptr;
-        const uint32_t* dcnt = nullptr;
-        if ((rc = src.feed(j, pass, r0, n, &drep, &dcnt, s))) goto done;
-        if (pass == 0) klsh::launch_kmc_union(drep, n, base[j] + r0, tab, first, mask, s, gc);
-        else klsh::launch_kmc_count(drep, dcnt, n, tab, mask, acc, s, gc);
-        KLSH_KHIP(hipGetLastError());
-        src.fed(j, pass, n);
-        KLSH_KHIP(hipStreamSynchronize(s));  // the source reuses its buffers for the next chunk
-      }
-      uint64_t nv = 0;
-      if ((rc = src.end(j, pass, &nv, &coverage[j], s))) goto done;
-      if (pass == 0) {
-        local.records_listed += nv;
-        // fewer listed than the total: KmcRead's vector keeps default (all-A) k-mers at the end
-        if (nv < total) {
-          const uint64_t zero = 0;
-          KLSH_KHIP(hipMemcpyAsync(dzero, &zero, 8, hipMemcpyHostToDevice, s));
-          klsh::launch_kmc_union(dzero, 1, base[j] + total, tab, first, mask, s, gc);
-          KLSH_KHIP(hipGetLastError());
-          KLSH_KHIP(hipStreamSynchronize(s));
-        }
-        base[j + 1] = base[j] + total + 1;
-      } else {
-        // this sample's column in output order (WriteHT, io/ioHT.cc:30-55)
-        klsh::launch_kmc_emit(acc, slots, kmap, col, s, gc);
-        KLSH_KHIP(hipGetLastError());
-        std::vector<uint16_t> hcol(kmap);
-        if (kmap) KLSH_KHIP(hipMemcpyAsync(hcol.data(), col, kmap * 2ull, hipMemcpyDeviceToHost, s));
-        KLSH_KHIP(hipStreamSynchronize(s));
-        if (kmap && fwrite(hcol.data(), 2, kmap, fb) != kmap) {
-          rc = set_error(KLSH_E_ARG, "kmer_count.bin: write failed");
-          goto done;
-        }
-      }
-    }
-    if (pass == 0) {
-      // first-appearance order: occupied slots sorted by their 64-bit ordinal (two stable
-      // 32-bit radix sorts, low word then high word)
-      KLSH_KHIP(hipMalloc((void**)&lo, (cap / 2 + 64) * 4));
-      KLSH_KHIP(hipMalloc((void**)&lo2, (cap / 2 + 64) * 4));
-      KLSH_KHIP(hipMalloc((void**)&slots, (cap / 2 + 64) * 4));
-      KLSH_KHIP(hipMalloc((void**)&slots2, (cap / 2 + 64) * 4));
-      KLSH_KHIP(hipMalloc((void**)&ws, klsh::sort_ws_words(cap / 2 + 64) * 4));
-      KLSH_KHIP(hipMemsetAsync(nvalid, 0, 4, s));
-      klsh::launch_kmc_collect(tab, first, cap, lo, slots, nvalid, s, gc);
-      KLSH_KHIP(hipGetLastError());
-      KLSH_KHIP(hipMemcpyAsync(&kmap, nvalid, 4, hipMemcpyDeviceToHost, s));
-      KLSH_KHIP(hipStreamSynchronize(s));
-      uint32_t *ok_ = nullptr, *ov_ = nullptr;
-      klsh::radix_sort(lo, slots, lo2, slots2, kmap, 32, ws, &ok_, &ov_, s);
-      const uint64_t last = base[n_samples];
-      int hbits = 0;
-      while (hbits < 32 && (last >> 32) >> hbits) ++hbits;
-      if (hbits) {
-        hooks.high_sort = 1;
-        uint32_t* hk = ok_ == lo ? lo2 : lo;  // the free key buffer
-        uint32_t* hv = ov_ == slots ? slots2 : slots;
-        klsh::launch_kmc_hi(first, ov_, kmap, hk, s, gc);
-        uint32_t *ok2 = nullptr, *ov2 = nullptr;
-        klsh::radix_sort(hk, ov_, ok_, hv, kmap, hbits, ws, &ok2, &ov2, s);
-        ov_ = ov2;
-      }
-      KLSH_KHIP(hipGetLastError());
-      if (ov_ != slots) KLSH_KHIP(hipMemcpyAsync(slots, ov_, kmap * 4ull, hipMemcpyDeviceToDevice, s));
-      KLSH_KHIP(hipMalloc((void**)&keys_out, (uint64_t)std::max<uint32_t>(kmap, 1) * 8));
-      KLSH_KHIP(hipMalloc((void**)&col, (uint64_t)std::max<uint32_t>(kmap, 1) * 2));
-      klsh::launch_kmc_emit_keys(tab, slots, kmap, keys_out, s, gc);
-      KLSH_KHIP(hipGetLastError());
-      std::vector<uint64_t> hkeys(kmap);
-      std::vector<uint32_t> hslots(kmap);
-      if (kmap) {
-        KLSH_KHIP(hipMemcpyAsync(hkeys.data(), keys_out, kmap * 8ull, hipMemcpyDeviceToHost, s));
-        KLSH_KHIP(hipMemcpyAsync(hslots.data(), slots, kmap * 4ull, hipMemcpyDeviceToHost, s));
-      }
-      KLSH_KHIP(hipStreamSynchronize(s));
-      if (hooks.keep_first) hooks.first = hkeys;
-      {  // the reference's row order: its libcuckoo table after the first-appearance inserts
-        const double tc = now_ms();
-        std::vector<uint64_t> hv(kmap);
-        for (uint32_t i = 0; i < kmap; ++i) hv[i] = kmer_hash(hkeys[i], (k + 3) / 4);
-        CuckooOrder table(hv, 16);
-        for (uint32_t i = 0; i < kmap; ++i) table.insert(i);
-        const std::vector<uint32_t> ord = table.order();
-        std::vector<uint64_t> k2(kmap);
-        std::vector<uint32_t> s2(kmap);
-        for (uint32_t i = 0; i < kmap; ++i) {
-          k2[i] = hkeys[ord[i]];
-          s2[i] = hslots[ord[i]];
-        }
-        hkeys.swap(k2);
-        if (kmap) KLSH_KHIP(hipMemcpyAsync(slots, s2.data(), kmap * 4ull, hipMemcpyHostToDevice, s));
-        KLSH_KHIP(hipStreamSynchronize(s));
-        local.order_ms = now_ms() - tc;
-      }
-      // kmer_set.hex: the k-mers' 8-byte images in row order (Kmer::writeBytes, kmer/Kmer.cc:307)
-      fh = fopen((dir + "kmer_set.hex").c_str(), "wb");
-      fb = fopen((dir + "kmer_count.bin").c_str(), "wb");
-      fl = fopen((dir + "kmer_count.log").c_str(), "w");
-      if (!fh || !fb || !fl) {
-        rc = set_error(KLSH_E_ARG, "cannot write kmer_set.hex / kmer_count.bin / kmer_count.log");
-        goto done;
-      }
-      if (kmap && fwrite(hkeys.data(), 8, kmap, fh) != kmap) {
-        rc = set_error(KLSH_E_ARG, "kmer_set.hex: write failed");
-        goto done;
-      }
-    }
-  }
-  // kmer_count.log: "%llu" kmap_size, then "\t%f" per sample coverage (io/ioHT.cc:170-187)
-  fprintf(fl, "%llu", (unsigned long long)kmap);
-  for (int j = 0; j < n_samples; ++j) fprintf(fl, "\t%f", (double)coverage[j]);
-  local.kmap_size = kmap;
-
-done:
-  if (fh) fclose(fh);
-  if (fb) fclose(fb);
-  if (fl) fclose(fl);
-  for (void* ptr : {(void*)tab, (void*)first, (void*)dzero, (void*)keys_out, (void*)acc,
-                    (void*)nvalid, (void*)lo, (void*)lo2, (void*)slots, (void*)slots2, (void*)ws,
-                    (void*)col})
-    if (ptr) (void)hipFree(ptr);
-  return rc;
+  KhBuild b(ctx, src, n_samples, k, st);
+  if (int rc = b.init()) return rc;
+  if (int rc = b.union_pass()) return rc;
+  if (int rc = b.order_rows(dir)) return rc;
+  if (int rc = b.count_pass()) return rc;
+  return b.write_log();
 }
 
 extern "C" int klsh_build_khtable(klsh_ctx* ctx, const char* const* kmc_names, int n_samples,

@@ -8,11 +8,13 @@
 //                 [min_count, max_count] are dropped (rep = all ones).  The k-mer becomes the
 //                 reference Kmer's 8-byte image (base i at bits 2i) and its canonical form
 //                 rep = (km < twin) ? km : twin in memcmp order (kmer/Kmer.cc:76-187).
-//   k_kmc_union   rep -> table slot (open addressing, 64-bit CAS), first[slot] = the smallest
+//   k_kmc_union   rep -> its slot of the k-mer table (klsh_kmer.h), first[slot] = the smallest
 //                 (sample, record) ordinal that listed it
 //   k_kmc_count   count[slot] += the record's counter (clamped at 65535 when written out: the
 //                 reference's per-step clamp, kmc_reader.cc:105-108, gives the same total)
-//   k_kmc_collect occupied slots -> (ordinal low / high words, slot) for the first-appearance order
+//   k_ktab_collect<ByFirst>  occupied slots -> (ordinal low word, slot) for the first-appearance
+//                 order; k_ktab_gather the words that order then needs: the ordinals' high words,
+//                 mode K's values' high words (order_slots_u64), the keys in row order
 //   k_kmc_emit    one sample's uint16 column in output order (WriteHT, io/ioHT.cc:30-55)
 #include <hip/hip_runtime.h>
 
@@ -22,17 +24,6 @@
 #include "klsh_kmer.h"
 
 namespace klsh {
-
-constexpr uint64_t kKmcEmpty = ~0ull;
-
-__device__ __forceinline__ uint64_t kmc_hash(uint64_t k) {  // murmur3 finalizer
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return k;
-}
 
 __global__ __launch_bounds__(256) void k_kmc_decode(const uint8_t* __restrict__ recs, uint64_t n,
                                                     uint64_t rec0, KmcParams kp,
@@ -55,7 +46,7 @@ __global__ __launch_bounds__(256) void k_kmc_decode(const uint8_t* __restrict__ 
     for (uint32_t b = 0; b < kp.sufix_size; ++b) suf = (suf << 8) | p[b];
     uint32_t c = 0;
     for (uint32_t b = 0; b < kp.counter_size; ++b) c |= (uint32_t)p[kp.sufix_size + b] << (8 * b);
-    uint64_t key = kKmcEmpty;
+    uint64_t key = kKtabEmpty;
     if (c >= kp.min_count && (uint64_t)c <= kp.max_count) {
       const uint64_t pre = lo & kp.prefix_mask;
       const uint64_t v = kp.p == 0 ? suf : (pre << (2 * (kp.k - kp.p))) | suf;  // s[0] on top
@@ -70,34 +61,13 @@ __global__ __launch_bounds__(256) void k_kmc_decode(const uint8_t* __restrict__ 
   if ((threadIdx.x & 63u) == 0 && valid) atomicAdd(n_valid, valid);
 }
 
-__device__ __forceinline__ uint64_t kmc_slot_insert(unsigned long long* tab, uint64_t mask,
-                                                    uint64_t key) {
-  uint64_t h = kmc_hash(key) & mask;
-  while (true) {
-    const unsigned long long prev = atomicCAS(&tab[h], (unsigned long long)kKmcEmpty,
-                                              (unsigned long long)key);
-    if (prev == kKmcEmpty || prev == key) return h;
-    h = (h + 1) & mask;
-  }
-}
-
-__device__ __forceinline__ uint64_t kmc_slot_find(const uint64_t* tab, uint64_t mask, uint64_t key) {
-  uint64_t h = kmc_hash(key) & mask;
-  while (true) {
-    const uint64_t t = tab[h];
-    if (t == key) return h;
-    if (t == kKmcEmpty) return ~0ull;
-    h = (h + 1) & mask;
-  }
-}
-
 __global__ __launch_bounds__(256) void k_kmc_union(const uint64_t* __restrict__ rep, uint64_t n,
                                                    uint64_t ord0, unsigned long long* tab,
                                                    unsigned long long* first, uint64_t mask) {
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull) {
     const uint64_t key = rep[i];
-    if (key == kKmcEmpty) continue;
-    const uint64_t h = kmc_slot_insert(tab, mask, key);
+    if (key == kKtabEmpty) continue;
+    const uint64_t h = ktab_claim(tab, mask, key);
     atomicMin(&first[h], (unsigned long long)(ord0 + i));
   }
 }
@@ -108,48 +78,26 @@ __global__ __launch_bounds__(256) void k_kmc_count(const uint64_t* __restrict__ 
                                                    uint32_t* __restrict__ acc) {
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull) {
     const uint64_t key = rep[i];
-    if (key == kKmcEmpty) continue;
-    const uint64_t h = kmc_slot_find(tab, mask, key);
+    if (key == kKtabEmpty) continue;
+    const uint64_t h = ktab_find(tab, mask, key);
     if (h != ~0ull) atomicAdd(&acc[h], min(cnt[i], 65535u));  // a sum past 65535 is clamped later
   }
 }
 
-__global__ __launch_bounds__(256) void k_kmc_collect(const uint64_t* __restrict__ tab,
-                                                     const uint64_t* __restrict__ first,
-                                                     uint64_t cap, uint32_t* __restrict__ lo,
-                                                     uint32_t* __restrict__ slot,
-                                                     uint32_t* __restrict__ n_out) {
-  // cap is a power of two >= 1024: every wave's 64 lanes are in or out of range together
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull;
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * 256ull) {
-    const bool occ = tab[i] != kKmcEmpty;
-    const uint64_t m = __ballot(occ);
-    if (!m) continue;
-    uint32_t base = 0;  // one add per wave, not per entry (a single counter)
-    if (lane == (uint32_t)__builtin_ctzll(m)) base = atomicAdd(n_out, (uint32_t)__popcll(m));
-    base = __shfl(base, (int)__builtin_ctzll(m), 64);
-    if (occ) {
-      const uint32_t o = base + (uint32_t)__popcll(m & below);
-      lo[o] = (uint32_t)first[i];
-      slot[o] = (uint32_t)i;
-    }
-  }
-}
+// k_ktab_collect's selection of mode B: every occupied slot, by its first-appearance ordinal
+struct ByFirst {
+  const uint64_t* first;
+  __device__ bool take(uint64_t) const { return true; }
+  __device__ uint32_t low(uint64_t i, uint64_t) const { return (uint32_t)first[i]; }
+};
 
-// hi[i] = high word of the first-appearance ordinal of slot slots[i]
-__global__ __launch_bounds__(256) void k_kmc_hi(const uint64_t* __restrict__ first,
-                                                const uint32_t* __restrict__ slots, uint64_t n,
-                                                uint32_t* __restrict__ hi) {
+// out[i] = src[idx[i]]: the whole word (T = uint64_t) or its high half (T = uint32_t)
+template <class T>
+__global__ __launch_bounds__(256) void k_ktab_gather(const uint64_t* __restrict__ src,
+                                                     const uint32_t* __restrict__ idx, uint64_t n,
+                                                     T* __restrict__ out) {
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull)
-    hi[i] = (uint32_t)(first[slots[i]] >> 32);
-}
-
-__global__ __launch_bounds__(256) void k_kmc_emit_keys(const uint64_t* __restrict__ tab,
-                                                       const uint32_t* __restrict__ order,
-                                                       uint64_t n, uint64_t* __restrict__ out) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull)
-    out[i] = tab[order[i]];
+    out[i] = (T)(src[idx[i]] >> (64 - 8 * sizeof(T)));
 }
 
 __global__ __launch_bounds__(256) void k_kmc_emit(const uint32_t* __restrict__ acc,
@@ -159,44 +107,39 @@ __global__ __launch_bounds__(256) void k_kmc_emit(const uint32_t* __restrict__ a
     out[i] = (uint16_t)min(acc[order[i]], 65535u);
 }
 
-static uint32_t grid_for(uint64_t n, uint32_t grid_cap) {
-  const uint64_t g = (n + 255) / 256;
-  return cap_grid((uint32_t)(g < 16384 ? (g ? g : 1) : 16384), grid_cap);
-}
-
 void launch_kmc_decode(const uint8_t* recs, uint64_t n, uint64_t rec0, const KmcParams& kp,
                        const uint64_t* lut, uint64_t lut_n, uint64_t* rep, uint32_t* cnt,
                        uint32_t* n_valid, hipStream_t s, uint32_t grid_cap) {
   if (n)
-    k_kmc_decode<<<grid_for(n, grid_cap), 256, 0, s>>>(recs, n, rec0, kp, lut, lut_n, rep, cnt,
+    k_kmc_decode<<<stride_grid(n, grid_cap), 256, 0, s>>>(recs, n, rec0, kp, lut, lut_n, rep, cnt,
                                                        n_valid);
 }
 void launch_kmc_union(const uint64_t* rep, uint64_t n, uint64_t ord0, uint64_t* tab,
                       uint64_t* first, uint64_t mask, hipStream_t s, uint32_t grid_cap) {
   if (n)
-    k_kmc_union<<<grid_for(n, grid_cap), 256, 0, s>>>(
+    k_kmc_union<<<stride_grid(n, grid_cap), 256, 0, s>>>(
         rep, n, ord0, reinterpret_cast<unsigned long long*>(tab),
         reinterpret_cast<unsigned long long*>(first), mask);
 }
 void launch_kmc_count(const uint64_t* rep, const uint32_t* cnt, uint64_t n, const uint64_t* tab,
                       uint64_t mask, uint32_t* acc, hipStream_t s, uint32_t grid_cap) {
-  if (n) k_kmc_count<<<grid_for(n, grid_cap), 256, 0, s>>>(rep, cnt, n, tab, mask, acc);
+  if (n) k_kmc_count<<<stride_grid(n, grid_cap), 256, 0, s>>>(rep, cnt, n, tab, mask, acc);
 }
 void launch_kmc_collect(const uint64_t* tab, const uint64_t* first, uint64_t cap, uint32_t* lo,
                         uint32_t* slot, uint32_t* n_out, hipStream_t s, uint32_t grid_cap) {
-  k_kmc_collect<<<grid_for(cap, grid_cap), 256, 0, s>>>(tab, first, cap, lo, slot, n_out);
+  k_ktab_collect<<<stride_grid(cap, grid_cap), 256, 0, s>>>(tab, ByFirst{first}, cap, lo, slot, n_out);
 }
-void launch_kmc_hi(const uint64_t* first, const uint32_t* slots, uint64_t n, uint32_t* hi,
-                   hipStream_t s, uint32_t grid_cap) {
-  if (n) k_kmc_hi<<<grid_for(n, grid_cap), 256, 0, s>>>(first, slots, n, hi);
+void launch_ktab_gather(const uint64_t* src, const uint32_t* idx, uint64_t n, uint32_t* hi,
+                        hipStream_t s, uint32_t grid_cap) {
+  if (n) k_ktab_gather<<<stride_grid(n, grid_cap), 256, 0, s>>>(src, idx, n, hi);
 }
-void launch_kmc_emit_keys(const uint64_t* tab, const uint32_t* order, uint64_t n, uint64_t* out,
-                          hipStream_t s, uint32_t grid_cap) {
-  if (n) k_kmc_emit_keys<<<grid_for(n, grid_cap), 256, 0, s>>>(tab, order, n, out);
+void launch_ktab_gather(const uint64_t* src, const uint32_t* idx, uint64_t n, uint64_t* out,
+                        hipStream_t s, uint32_t grid_cap) {
+  if (n) k_ktab_gather<<<stride_grid(n, grid_cap), 256, 0, s>>>(src, idx, n, out);
 }
 void launch_kmc_emit(const uint32_t* acc, const uint32_t* order, uint64_t n, uint16_t* out,
                      hipStream_t s, uint32_t grid_cap) {
-  if (n) k_kmc_emit<<<grid_for(n, grid_cap), 256, 0, s>>>(acc, order, n, out);
+  if (n) k_kmc_emit<<<stride_grid(n, grid_cap), 256, 0, s>>>(acc, order, n, out);
 }
 
 }  // namespace klsh

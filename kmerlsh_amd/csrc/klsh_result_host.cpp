@@ -19,16 +19,16 @@ static int device_result(klsh_ctx* ctx, uint32_t* d_off, uint32_t* d_nodes, uint
   const bool rank = (d_nodes || d_labels) && M;
   const uint32_t cap = ctx->mw.grid_cap;
   hipStream_t s = ctx->stream;
-  uint32_t *hdr = nullptr, *tsum = nullptr, *off_tmp = nullptr, *rowof = nullptr;
-  uint64_t *st0 = nullptr, *st1 = nullptr;
+  klsh::DevBuf<uint32_t> hdr, tsum, off_tmp, rowof;
+  klsh::DevBuf<uint64_t> st0, st1;
   uint32_t h[klsh::kResHdrWords] = {};
   int rc = 0;
   do {
     const uint32_t ntiles = klsh::result_tiles(n);
-    if ((rc = dalloc(&hdr, klsh::kResHdrWords)) || (rc = dalloc(&tsum, 2 * (size_t)ntiles))) break;
-    if (!d_off && (rc = dalloc(&off_tmp, n + 1))) break;
-    if (rank && ((rc = dalloc(&st0, M)) || (rc = dalloc(&st1, M)) || (rc = dalloc(&rowof, M)))) break;
-    uint32_t* off = d_off ? d_off : off_tmp;
+    if ((rc = dalloc(hdr, klsh::kResHdrWords)) || (rc = dalloc(tsum, 2 * (size_t)ntiles))) break;
+    if (!d_off && (rc = dalloc(off_tmp, n + 1))) break;
+    if (rank && ((rc = dalloc(st0, M)) || (rc = dalloc(st1, M)) || (rc = dalloc(rowof, M)))) break;
+    uint32_t* off = d_off ? d_off : off_tmp.get();
     if (hipMemsetAsync(hdr, 0, sizeof(h), s) != hipSuccess) {
       rc = fail(KLSH_E_HIP, "result header reset");
       break;
@@ -82,7 +82,6 @@ static int device_result(klsh_ctx* ctx, uint32_t* d_off, uint32_t* d_nodes, uint
       rc = fail(KLSH_E_STATE, "corrupt member list");
   } while (false);
   (void)hipStreamSynchronize(s);
-  dfree(hdr); dfree(tsum); dfree(off_tmp); dfree(rowof); dfree(st0); dfree(st1);
   return rc;
 }
 
@@ -118,23 +117,19 @@ int klsh_result(klsh_ctx* ctx, float* rows, uint64_t* member_offsets, uint64_t* 
   const uint64_t n = ctx->n_live;
   hipStream_t s = ctx->stream;
   if (rows && n) {
-    float* tmp = nullptr;
-    if (int e = dalloc(&tmp, n * (uint64_t)ctx->d)) return e;
+    klsh::DevBuf<float> tmp;
+    if (int e = dalloc(tmp, n * (uint64_t)ctx->d)) return e;
     klsh::launch_gather_rows(ctx->rows, ctx->order, (uint32_t)n, tmp, s);
     hipError_t e1 = hipMemcpyAsync(rows, tmp, sizeof(float) * n * ctx->d, hipMemcpyDeviceToHost, s);
     hipError_t e2 = hipStreamSynchronize(s);
-    dfree(tmp);
     if (e1 != hipSuccess || e2 != hipSuccess) return fail(KLSH_E_HIP, "result rows copy");
   }
   if ((member_offsets || member_ids) && ctx->result_device) {
     // offsets and nodes from the kernels, then one streaming pass: member_ids[m] = ids[nodes[m]]
     const uint64_t M = ctx->members;
-    uint32_t *d_off = nullptr, *d_nodes = nullptr;
+    klsh::DevBuf<uint32_t> d_off, d_nodes;
     int rc = 0;
-    if ((rc = dalloc(&d_off, n + 1)) || (member_ids && (rc = dalloc(&d_nodes, M)))) {
-      dfree(d_off);
-      return rc;
-    }
+    if ((rc = dalloc(d_off, n + 1)) || (member_ids && (rc = dalloc(d_nodes, M)))) return rc;
     uint64_t total = 0;
     std::vector<uint32_t> off(n + 1), nodes;
     if (!(rc = device_result(ctx, d_off, d_nodes, nullptr, &total))) {  // (total <= M)
@@ -144,8 +139,6 @@ int klsh_result(klsh_ctx* ctx, float* rows, uint64_t* member_offsets, uint64_t* 
            hipMemcpy(nodes.data(), d_nodes, 4 * total, hipMemcpyDeviceToHost) != hipSuccess))
         rc = fail(KLSH_E_HIP, "result lists copy");
     }
-    dfree(d_off);
-    dfree(d_nodes);
     if (rc) return rc;
     if (member_offsets)
       for (uint64_t i = 0; i <= n; ++i) member_offsets[i] = off[i];
@@ -208,12 +201,11 @@ int klsh_labels(klsh_ctx* ctx, uint32_t* labels) {
   if (!labels && ctx->members) return fail(KLSH_E_ARG, "null argument");
   KLSH_HIP(hipSetDevice(ctx->device));
   if (ctx->members == 0) return 0;
-  uint32_t* d_labels = nullptr;
-  if (int e = dalloc(&d_labels, ctx->members)) return e;
+  klsh::DevBuf<uint32_t> d_labels;
+  if (int e = dalloc(d_labels, ctx->members)) return e;
   int rc = device_result(ctx, nullptr, nullptr, d_labels, nullptr);
   if (!rc && hipMemcpy(labels, d_labels, 4 * ctx->members, hipMemcpyDeviceToHost) != hipSuccess)
     rc = fail(KLSH_E_HIP, "labels copy");
-  dfree(d_labels);
   return rc;
 }
 

@@ -23,7 +23,7 @@ from kmc_inputs import write_db
 from mode_e_inputs import SplitMix, revcomp
 
 # lut_prefix_length per k: (k - p) % 4 == 0
-PREFIX = {1: 1, 4: 0, 5: 1, 21: 9, 31: 11, 32: 12}
+PREFIX = {1: 1, 4: 0, 5: 1, 16: 8, 17: 9, 21: 9, 31: 11, 32: 12}
 
 CASES = {
     # 3 + 3 samples from shared genomes, both strands, reads of 60..150 bases; lower case, N at the
@@ -43,6 +43,12 @@ CASES = {
                gz=(), crlf=(), multiline=(), extra=("ACGTACGTACGT", "AATTAATT", "acgtNAATT")),
     "k5": dict(k=5, count_min=2, n1=1, n2=2, genomes=2, glen=150, reads=50, rlen=(5, 70), seed=433,
                gz=(2,), crlf=(), multiline=(0,)),
+    # the edge of the listing's order by a 2k-bit value: k = 16 is one sort over exactly 32 bits,
+    # k = 17 adds the pass over the values' high words, 2 bits wide
+    "k16": dict(k=16, count_min=2, n1=1, n2=1, genomes=2, glen=200, reads=150, rlen=(16, 80),
+                seed=457, gz=(), crlf=(), multiline=()),
+    "k17": dict(k=17, count_min=2, n1=1, n2=1, genomes=2, glen=200, reads=150, rlen=(17, 80),
+                seed=461, gz=(), crlf=(), multiline=()),
     # saturation: see _sat_samples
     "sat": dict(k=21, count_min=2, n1=1, n2=1, genomes=1, glen=200, reads=30, rlen=(60, 120),
                 seed=439, gz=(), crlf=(), multiline=()),

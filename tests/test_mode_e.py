@@ -238,3 +238,28 @@ def test_extract_fastq_batches_match_single_call(engine, tmp_path):
     assert (tmp_path / "out.fq").read_bytes() == expect
     assert st["reads"] == n and st["reads_extracted"] == int(flags.sum())
     assert 0 < st["reads_extracted"] < n
+
+
+@pytest.mark.gpu
+def test_extract_error_leaves_the_context_usable(engine, tmp_path):
+    """klsh_extract_fastq with an output path in a directory that does not exist is an error (the
+    input is open by then); the next call on the same context and set writes exactly the records
+    the oracle's vote selects."""
+    from kmerlsh_amd import _native
+
+    k, vote = 21, 0.4
+    rng = np.random.default_rng(78)
+    src = rng.choice(list(b"ACGT"), size=20000).astype(np.uint8).tobytes()
+    kset = np.unique(oe.canonical_kmers(src[:12000], k))
+    reads = random_reads(rng, 300, src, k)
+    lines = [b"@r%d\n%s\n+\n%s\n" % (i, s, b"I" * len(s)) for i, s in enumerate(reads)]
+    path = tmp_path / "in.fq"
+    path.write_bytes(b"".join(lines))
+    ks = _native.KmerSet(engine, kset)
+    with pytest.raises(_native.KlshError, match="cannot open for writing"):
+        ks.extract_fastq(str(path), str(tmp_path / "no_such_dir" / "out.fq"), k, vote)
+    st = ks.extract_fastq(str(path), str(tmp_path / "out.fq"), k, vote)
+    ks.close()
+    _, flags = oe.check_reads(reads, kset, k, vote)
+    assert (tmp_path / "out.fq").read_bytes() == b"".join(lines[i] for i in np.nonzero(flags)[0])
+    assert st["reads"] == len(reads) and 0 < st["reads_extracted"] == int(flags.sum()) < len(reads)

@@ -112,6 +112,18 @@ def test_fixtures_reach_what_they_are_for(cases):
     assert occ["ACGT"] >= 2 and occ["AATT"] >= 2  # palindromes: one occurrence per window
     assert kc.count_occurrences(["ACGTACGT"], 4)["ACGT"] == 2
 
+    # the listing's order by a 2k-bit value: at k = 16 the one sort uses all 32 bits, at k = 17 the
+    # low words alone do not order the listing (the pass over the high words is needed)
+    for name in ("k16", "k17"):
+        for ls in cases(name).listings:
+            vals = [ki.kmer_value(w) for w, _ in ls]
+            lows = [v & 0xFFFFFFFF for v in vals]
+            assert vals == sorted(vals) and len(vals) > 300
+            if name == "k16":
+                assert max(vals) >> 31 == 1
+            else:
+                assert max(vals) >> 32 == 3 and lows != sorted(lows)
+
     k21 = cases("k21")
     seqs = [s for ss in k21.info["seqs"] for s in ss]
     assert any(s.startswith("N") for s in seqs) and any(s.endswith("N") for s in seqs)
@@ -314,6 +326,29 @@ def test_errors_leave_the_context_usable(engine, cases, tmp_path):
     assert (tmp_path / "kmer_count.log").read_text() == fx["log"]
     assert hashlib.md5((tmp_path / "kmer_set.hex").read_bytes()).hexdigest() == fx["hex_md5"]
     assert hashlib.md5((tmp_path / "kmer_count.bin").read_bytes()).hexdigest() == fx["bin_md5"]
+
+
+@pytest.mark.gpu
+def test_missing_second_sample_leaves_the_context_usable(engine, cases, tmp_path):
+    """klsh_count_kmc whose second sample's FASTQ is missing fails on the host ("cannot open"),
+    writes nothing, and the next call on the same context writes k5's files."""
+    from kmerlsh_amd import _native
+
+    c, fx = cases("k5"), fixtures()["k5"]
+    bad, good = tmp_path / "bad", tmp_path / "good"
+    bad.mkdir()
+    good.mkdir()
+    paths = [c.fastq[0], str(tmp_path / "missing.fq")] + c.fastq[2:]
+    with pytest.raises(_native.KlshError, match="cannot open"):
+        engine.count_kmc(paths, [str(bad / ("s%d" % j)) for j in range(len(paths))], c.k,
+                         c.count_min, str(bad))
+    assert not any(bad.iterdir())
+    dbs = [str(good / ("s%d" % j)) for j in range(len(c.fastq))]
+    st, dst = engine.count_kmc(c.fastq, dbs, c.k, c.count_min, str(good))
+    assert st["kmap_size"] == fx["kmap"] and dst["databases"] == len(dbs)
+    assert (good / "kmer_count.log").read_text() == fx["log"]
+    assert hashlib.md5((good / "kmer_set.hex").read_bytes()).hexdigest() == fx["hex_md5"]
+    assert hashlib.md5((good / "kmer_count.bin").read_bytes()).hexdigest() == fx["bin_md5"]
 
 
 @pytest.mark.gpu
