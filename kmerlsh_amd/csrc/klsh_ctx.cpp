@@ -89,16 +89,16 @@ int klsh_ctx::reserve_words(uint32_t** p, size_t* cap, size_t words) {
 void klsh_ctx::release_state() {
   dfree(rows.x); dfree(rows.nrm); dfree(rows.cnt); dfree(rows.head); dfree(rows.tail);
   dfree(rows.nxt); dfree(order); dfree(alt); dfree(keys); dfree(keys2); dfree(nk1);
-  dfree(nk2); dfree(nv2); dfree(hist); dfree(tile_sums); dfree(mw.over); dfree(mw.run_ws);
-  dfree(mw.huge);
-  dfree(mw.long_P);
-  mw.long_groups = 0;
-  dfree(pw.fix);
-  dfree(pw.ws);
-  pw.cap = 0;
-  for (auto& c : mw.big) dfree(c);
-  for (auto& c : mw.cls) dfree(c);
-  for (auto& c : mw.act) dfree(c);
+  dfree(nk2); dfree(nv2); dfree(hist); dfree(tile_sums); dfree(mp.lists.over); dfree(mp.run_ws);
+  dfree(mp.lists.huge);
+  dfree(mp.lists.long_P);
+  mp.long_groups = 0;
+  dfree(pp.v.fix);
+  dfree(pp.v.ws);
+  pp.v.cap = 0;
+  for (auto& c : mp.lists.big) dfree(c);
+  for (auto& c : mp.lists.cls) dfree(c);
+  for (auto& c : mp.lists.act) dfree(c);
   dfree(kstamp);
   dfree(lb.status);
   dfree(xh_alloc);
@@ -135,7 +135,7 @@ void klsh_ctx::release() {
   dfree(W);
   dfree(ctr);
   dfree(rc);
-  mw.rc = nullptr;
+  mp.lists.rc = nullptr;
   if (h_ctr) (void)hipHostFree(h_ctr);
   h_ctr = nullptr;
   dfree(n_next_dev);
@@ -149,28 +149,28 @@ void klsh_ctx::release() {
   if (counts_ev) (void)hipEventDestroy(counts_ev);
   counts_ev = nullptr;
   for (int i = 0; i < klsh::kMergeStreams; ++i) {
-    if (mw.join[i]) (void)hipEventDestroy(mw.join[i]);
-    if (mw.aux[i]) (void)hipStreamDestroy(mw.aux[i]);
-    mw.join[i] = nullptr;
-    mw.aux[i] = nullptr;
+    if (mp.join[i]) (void)hipEventDestroy(mp.join[i]);
+    if (mp.aux[i]) (void)hipStreamDestroy(mp.aux[i]);
+    mp.join[i] = nullptr;
+    mp.aux[i] = nullptr;
   }
-  if (mw.fork) (void)hipEventDestroy(mw.fork);
-  mw.fork = nullptr;
+  if (mp.fork) (void)hipEventDestroy(mp.fork);
+  mp.fork = nullptr;
   if (stream) (void)hipStreamDestroy(stream);
   stream = nullptr;
 }
 
 int klsh_ctx::ensure_long(uint64_t s, int d_) {
-  const uint32_t want = klsh::long_ok(d_) && s >= 897 && mw.long_off != 1u
+  const uint32_t want = klsh::long_ok(d_) && s >= 897 && mp.long_off != 1u
                             ? (uint32_t)std::min<uint64_t>(256, s / 897 + 1)
                             : 0u;
-  if (want && want <= mw.long_groups) return 0;
-  dfree(mw.long_P);
-  mw.long_groups = 0;
+  if (want && want <= mp.long_groups) return 0;
+  dfree(mp.lists.long_P);
+  mp.long_groups = 0;
   if (!want) return 0;
-  if (int e = dalloc(&mw.long_P, (size_t)want * klsh::kLongRows * (klsh::kLongRows / 64)))
+  if (int e = dalloc(&mp.lists.long_P, (size_t)want * klsh::kLongRows * (klsh::kLongRows / 64)))
     return e;
-  mw.long_groups = want;
+  mp.long_groups = want;
   return 0;
 }
 
@@ -203,23 +203,23 @@ int klsh_ctx::reserve(uint64_t ns, uint64_t nm, int d_) {
       (e = dalloc(&nv2, s)) ||
       (e = dalloc(&hist, klsh::sort_ws_words(s))) ||
       (e = dalloc(&tile_sums, klsh::scan_ws_words(s))) ||
-      (e = dalloc(&mw.over, s + 64)) || (e = dalloc(&mw.run_ws, klsh::run_ws_words(s))) ||
-      (e = dalloc(&pw.fix, s)) || (e = dalloc(&pw.ws, 64)) ||
-      (e = dalloc(&mw.big[0], s / 65 + 64)) || (e = dalloc(&mw.big[1], s / 129 + 64)) ||
-      (e = dalloc(&mw.big[2], s / 193 + 64)) || (e = dalloc(&mw.big[3], s / 385 + 64)) ||
-      (e = dalloc(&mw.huge, s / 897 + 64)))
+      (e = dalloc(&mp.lists.over, s + 64)) || (e = dalloc(&mp.run_ws, klsh::run_ws_words(s))) ||
+      (e = dalloc(&pp.v.fix, s)) || (e = dalloc(&pp.v.ws, 64)) ||
+      (e = dalloc(&mp.lists.big[0], s / 65 + 64)) || (e = dalloc(&mp.lists.big[1], s / 129 + 64)) ||
+      (e = dalloc(&mp.lists.big[2], s / 193 + 64)) || (e = dalloc(&mp.lists.big[3], s / 385 + 64)) ||
+      (e = dalloc(&mp.lists.huge, s / 897 + 64)))
     return bail(e);
   if (shadow_wanted(d_))  // (in the large-buffer group: see below)
     if ((e = dalloc(&xh_alloc, s * dp_))) return bail(e);
   if ((e = ensure_long(s, d_))) return bail(e);
   for (int c = 0; c < klsh::kGroupClasses; ++c)
-    if ((e = dalloc(&mw.cls[c], klsh::group_class_capacity(c, s))) ||
-        (e = dalloc(&mw.act[c], klsh::group_class_capacity(c, s))))
+    if ((e = dalloc(&mp.lists.cls[c], klsh::group_class_capacity(c, s))) ||
+        (e = dalloc(&mp.lists.act[c], klsh::group_class_capacity(c, s))))
       return bail(e);
   // the look-back workspaces start zeroed (tickets, done counters, epochs, histograms) and the
   // kernels return them to zero; they are never cleared again
-  pw.cap = (uint32_t)s;
-  if (hipMemset(pw.ws, 0, sizeof(uint32_t) * 64) != hipSuccess ||
+  pp.v.cap = (uint32_t)s;
+  if (hipMemset(pp.v.ws, 0, sizeof(uint32_t) * 64) != hipSuccess ||
       hipMemset(hist, 0, sizeof(uint32_t) * klsh::sort_ws_words(s)) != hipSuccess ||
       hipMemset(tile_sums, 0, sizeof(uint32_t) * klsh::scan_ws_words(s)) != hipSuccess)
     return bail(fail(KLSH_E_HIP, "workspace init"));
@@ -239,7 +239,7 @@ int klsh_ctx::reserve(uint64_t ns, uint64_t nm, int d_) {
       return bail(fail(KLSH_E_HIP, "stamp / look-back init"));
     lb.epoch = 0;
   }
-  mw.tile_sums = tile_sums;
+  mp.tile_sums = tile_sums;
   cap_slots = s;
   cap_members = m;
   cap_dp = dp_;
@@ -481,17 +481,17 @@ klsh_ctx* klsh_create(int device, int* err) {
   for (auto& e : c->sev) ok = ok && hipEventCreateWithFlags(&e, tflags) == hipSuccess;
   for (int i = 0; i < klsh::kMergeStreams; ++i) {
     const bool hi = i == 0;  // (the 65..192-row stream high too: measured equal)
-    ok = ok && hipStreamCreateWithPriority(&c->mw.aux[i], hipStreamNonBlocking,
+    ok = ok && hipStreamCreateWithPriority(&c->mp.aux[i], hipStreamNonBlocking,
                                            (hi && big_prio) ? prio_hi : prio_lo) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&c->mw.join[i], oflags) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&c->mp.join[i], oflags) == hipSuccess;
   }
-  ok = ok && hipEventCreateWithFlags(&c->mw.fork, oflags) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&c->mp.fork, oflags) == hipSuccess;
   ok = ok && hipMalloc((void**)&c->ctr, sizeof(Counters)) == hipSuccess;
   ok = ok && hipHostMalloc((void**)&c->h_ctr, sizeof(Counters), hipHostMallocDefault) == hipSuccess;
   ok = ok && hipMemset(c->ctr, 0, sizeof(Counters)) == hipSuccess;  // err starts clear
   ok = ok && hipMalloc((void**)&c->rc, sizeof(klsh::RunCounters)) == hipSuccess &&
        hipMemset(c->rc, 0, sizeof(klsh::RunCounters)) == hipSuccess;
-  c->mw.rc = c->rc;
+  c->mp.lists.rc = c->rc;
   ok = ok && hipMalloc((void**)&c->n_next_dev, 64) == hipSuccess &&
        hipMemset(c->n_next_dev, 0, 64) == hipSuccess;
   if (ok && c->zero_copy) {
@@ -599,7 +599,7 @@ int klsh_load_rows_device(klsh_ctx* ctx, const float* d_rows, uint64_t n, int d,
                               sizeof(float) * row_stride, sizeof(float) * d, n,
                               hipMemcpyDeviceToDevice, s));
   }
-  klsh::launch_init_singletons(ctx->rows, ctx->order, (uint32_t)n, s, ctx->mw.grid_cap);
+  klsh::launch_init_singletons(ctx->rows, ctx->order, (uint32_t)n, s, ctx->grid_cap);
   klsh::launch_norms(ctx->rows, (uint32_t)n, s);
   KLSH_HIP(hipGetLastError());
   ctx->ids.resize(n);

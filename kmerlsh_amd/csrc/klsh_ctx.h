@@ -58,7 +58,7 @@ void dfree(T*& p) {
 
 // Owners of what a function or an object allocates for its own lifetime: device memory, pinned
 // host memory, an event, an open file.  Move-only; the destructor releases.  (The long-lived
-// members of klsh_ctx, Rows, MergeWork and Snapshot stay raw pointers: they are passed to kernels
+// members of klsh_ctx, Rows, RunLists and Snapshot stay raw pointers: they are passed to kernels
 // by value and released in release().)
 template <class T, bool Pinned = false>
 class DevBuf {
@@ -120,7 +120,7 @@ struct FileClose {
 using File = std::unique_ptr<FILE, FileClose>;
 
 // The (row, hyperplane) pairs the certified projection screens left to the exact chains, from a
-// copy of ProjectWork::ws: ws[4..6) the wide-row fix-up kernel's total, ws[32..64) the fp16
+// copy of ProjectView::ws: ws[4..6) the wide-row fix-up kernel's total, ws[32..64) the fp16
 // screen's 16 counters.
 inline uint64_t proj_close_pairs(const uint32_t (&w)[64]) {
   unsigned long long fixed = 0, part = 0;
@@ -259,8 +259,9 @@ struct klsh_ctx {
   uint32_t* nv2 = nullptr;
   uint32_t* hist = nullptr;
   uint32_t* tile_sums = nullptr;
-  klsh::MergeWork mw{};
-  klsh::ProjectWork pw{};     // wide-row matrix-core projection: fix-up list
+  klsh::MergePlan mp{};
+  uint32_t grid_cap = 0;  // option "grid_cap" (tests; 0 = off): every unit's launches (cap_grid)
+  klsh::ProjectPlan pp{};     // wide-row matrix-core projection: fix-up list
   Counters* ctr = nullptr;
   Counters* h_ctr = nullptr;  // pinned
   float* W = nullptr;         // hyperplane pool on the device, [k - w_k0][dp]
@@ -337,7 +338,7 @@ struct klsh_ctx {
   // writes it too (store_row4 / store_row1)
   uint16_t* xh_alloc = nullptr;
   bool shadow_wanted(int d_) const {
-    return pw.variant != klsh::kProjPacked && klsh::shadow_width_ok(d_);
+    return pp.variant != klsh::kProjPacked && klsh::shadow_width_ok(d_);
   }
   // Queued tail batches (run_batched; option "tail_batch", default on), their bucket sort as a
   // top-bits pass + the LDS bucket sort that lists the runs (option "tail_local", default on)
@@ -370,8 +371,8 @@ struct klsh_ctx {
   // canonical order and runs the remaining iterations on its replica — identically, with no
   // communication.  klsh_set_option(ctx, "shard_min_rows", n); 0 = always sharded.
   uint64_t shard_min_rows = 1u << 21;
-  uint32_t huge_quiet = 0;  // consecutive iterations without >896-row runs (MergeWork::huge_fold)
-  bool huge_fold_always = false;  // option "huge_fold" (tests): fold in every iteration
+  // an iteration over n live rows runs sharded (a bound group, above the threshold)
+  bool shards(uint64_t n) const { return comm && n >= shard_min_rows; }
   // option "comm_timeout_s": a collective that has not completed after this long aborts the group
   double comm_timeout_s = 600.0;
 

@@ -608,7 +608,7 @@ klsh_kset* klsh_kset_create(klsh_ctx* ctx, const uint64_t* kmers, uint64_t n, in
   ok = ok && hipMemsetAsync(ks->tab, 0xFF, cap * 8, s) == hipSuccess;
   ok = ok && (n == 0 || hipMemcpyAsync(dk, kmers, n * 8, hipMemcpyHostToDevice, s) == hipSuccess);
   if (ok) {
-    klsh::launch_kset_insert(dk, n, ks->tab, ks->mask, s, ctx->mw.grid_cap);
+    klsh::launch_kset_insert(dk, n, ks->tab, ks->mask, s, ctx->grid_cap);
     ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
   }
   if (!ok) return bad(set_error(KLSH_E_NOMEM, "k-mer set allocation / upload failed"));
@@ -641,7 +641,7 @@ int klsh_check_reads(klsh_ctx* ctx, const klsh_kset* ks, const char* seq,
   KLSH_HIP(dflag.alloc(n_reads));
   if (int rc = b.upload(seq + read_offsets[0], nb, off.data(), n_reads, nb + 64, s)) return rc;
   klsh::launch_check_reads(b.seq, b.off, n_reads, k, kmer_vote, ks->tab, ks->mask, dhit, dflag, s,
-                           ctx->mw.grid_cap);
+                           ctx->grid_cap);
   KLSH_HIP(hipGetLastError());
   if (hits) KLSH_HIP(hipMemcpyAsync(hits, dhit, n_reads * 4, hipMemcpyDeviceToHost, s));
   KLSH_HIP(hipMemcpyAsync(flags, dflag, n_reads, hipMemcpyDeviceToHost, s));
@@ -699,7 +699,7 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
       return e;
     KLSH_HIP(hipEventRecord(sl.dev.e0, s));
     klsh::launch_check_reads(sl.dev.seq, sl.dev.off, sl.n, k, kmer_vote, ks->tab, ks->mask, sl.dhit,
-                             sl.dflag, s, ctx->mw.grid_cap);
+                             sl.dflag, s, ctx->grid_cap);
     KLSH_HIP(hipGetLastError());
     KLSH_HIP(hipEventRecord(sl.dev.e1, s));
     KLSH_HIP(hipMemcpyAsync(sl.hflag, sl.dflag, sl.n, hipMemcpyDeviceToHost, s));

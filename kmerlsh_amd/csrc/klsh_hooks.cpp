@@ -105,10 +105,8 @@ int klsh_hash_keys(klsh_ctx* ctx, const float* rows, uint64_t n, int d, const fl
       (e = dalloc(W, (uint64_t)std::max(h, 1) * dp)) || (e = dalloc(fix, n)) ||
       (e = dalloc(ws, 64)) || (image && (e = dalloc(xh, n * dp))))
     return e;
-  klsh::ProjectWork pw = ctx->pw;  // the context's launch options, fresh workspaces
-  pw.fix = fix;
-  pw.ws = ws;
-  pw.cap = (uint32_t)n;
+  // the context's launch options over fresh workspaces
+  const klsh::ProjectPlan pp = ctx->pp.over(fix, ws, (uint32_t)n);
   r.x = x;
   r.xh = xh;
   hipStream_t s = ctx->stream;
@@ -118,7 +116,7 @@ int klsh_hash_keys(klsh_ctx* ctx, const float* rows, uint64_t n, int d, const fl
   if (hipMemsetAsync(r.x, 0, sizeof(float) * n * dp, s) != hipSuccess ||
       hipMemcpy2DAsync(r.x, 4 * dp, rows, 4 * d, 4 * d, n, hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemsetAsync(W, 0, sizeof(float) * std::max(h, 1) * dp, s) != hipSuccess ||
-      hipMemsetAsync(pw.ws, 0, sizeof(uint32_t) * 64, s) != hipSuccess ||
+      hipMemsetAsync(pp.v.ws, 0, sizeof(uint32_t) * 64, s) != hipSuccess ||
       (h > 0 && hipMemcpy2DAsync(W, 4 * dp, table, 4 * d, 4 * d, h, hipMemcpyHostToDevice, s) !=
                     hipSuccess) ||
       hipMemcpyAsync(slots, iota.data(), 4 * n, hipMemcpyHostToDevice, s) != hipSuccess) {
@@ -126,12 +124,12 @@ int klsh_hash_keys(klsh_ctx* ctx, const float* rows, uint64_t n, int d, const fl
   } else {
     if (image) klsh::launch_shadow_build(r, n, s);
     int variant = klsh::kPvNone;
-    const int kern = klsh::launch_project(r, slots, dkeys, (uint32_t)n, W, h, 0u, s, &pw,
+    const int kern = klsh::launch_project(r, slots, dkeys, (uint32_t)n, W, h, 0u, s, &pp,
                                           klsh::kNoTime, &variant);
     uint32_t w[64];
     if (hipGetLastError() != hipSuccess ||
         hipMemcpyAsync(keys, dkeys, 4 * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(w, pw.ws, sizeof(w), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(w, pp.v.ws, sizeof(w), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) {
       rc = fail(KLSH_E_HIP, "projection");
     } else {
@@ -208,14 +206,14 @@ int klsh_bucket_runs(klsh_ctx* ctx, const uint32_t* sorted_keys, uint64_t n, int
   for (int c = 0; c < kBigClasses && !e; ++c)
     e = dalloc(big[c], n / ((c ? klsh::kBigRows[c - 1] : 64) + 1) + 64);
   if (e) return e;
-  klsh::MergeWork w{};
-  w.run_ws = run_ws;
+  klsh::MergePlan plan{};  // the lists of this call, no options
+  plan.run_ws = run_ws;
+  klsh::RunLists& w = plan.lists;
   w.huge = huge;
   w.over = over;
   for (int c = 0; c < kGroupClasses; ++c) w.cls[c] = cls[c];
   for (int c = 0; c < kBigClasses; ++c) w.big[c] = big[c];
   w.rc = rc;
-  w.kt = klsh::kNoTime;
   hipStream_t s = ctx->stream;
   klsh::RunCounters hc{};
   int rc_ = 0;
@@ -223,7 +221,7 @@ int klsh_bucket_runs(klsh_ctx* ctx, const uint32_t* sorted_keys, uint64_t n, int
       hipMemcpyAsync(dk, sorted_keys, 4 * n, hipMemcpyHostToDevice, s) != hipSuccess) {
     rc_ = fail(KLSH_E_HIP, "upload");
   } else {
-    klsh::launch_runs(dk, 0, (uint32_t)n, bucket_thr, w, s);
+    klsh::launch_runs(dk, 0, (uint32_t)n, bucket_thr, plan, klsh::MergeCall{}, s);
     if (hipGetLastError() != hipSuccess ||
         hipMemcpyAsync(&hc, rc, sizeof(hc), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
@@ -261,8 +259,7 @@ int klsh_pcluster(klsh_ctx* ctx, float thr) {
   if (n == 0) return 0;
   hipStream_t s = ctx->stream;
   if (int e = ctx->reset_counters()) return e;
-  ctx->mw.huge_fold = ctx->huge_fold_always ? 1u : 0u;
-  ctx->mw.huge_cap = 0;
+  ctx->mp.no_counts();
   KLSH_HIP(hipMemsetAsync(ctx->keys, 0, 4ull * n, s));  // one bucket: every key equal
   uint64_t dummy = 0;
   if (int e = klsh::merge_and_compact(ctx, ctx->keys, ctx->order, n, thr, -1, 0, &dummy, nullptr,

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "klsh.h"
@@ -117,51 +118,54 @@ struct KTime {
   int set;
   int fold;
   int phase = -1;  // >= 0: the launch also stamps this phase class (its first start, last end)
+  KTime with_fold(int f) const { KTime k = *this; k.fold = f; return k; }
+  KTime with_phase(int p) const { KTime k = *this; k.phase = p; return k; }
 };
 constexpr KTime kNoTime{nullptr, 0, -1, -1};
 // Fold set `t` into the totals and clear it (one workgroup; device code, klsh_device.h).
 
-// Merge workspace (device), sized for `cap` positions.
-struct MergeWork {
-  uint2* cls[kGroupClasses];       // (start, length) of runs per size class
-  // the runs of each class the fp16 screen could not rule out (k_small_screen), and whether the
-  // small-run merge reads these instead of cls (set per launch)
+// The merge workspace by lifetime: what device code reads (MergeView and its parts), what the host
+// keeps (MergePlan), what holds for one call (MergeCall).  First the run lists of an iteration:
+struct RunLists {
+  uint2* cls[kGroupClasses];  // (start, length) of runs per size class
+  // the runs of each class the fp16 screen could not rule out (k_small_screen)
   uint2* act[kGroupClasses];
-  uint32_t screened;
-  uint2* big[kBigClasses];         // (start, length) of runs for k_merge_big, per class
-  uint2* huge;                     // (start, length) of runs for k_merge_huge
-  uint2* over;                     // (start, length) of oversize runs
-  uint32_t* tile_sums;
-  RunCounters* rc;                 // the run counts of this iteration (device)
-  uint32_t* run_ws;                // run finding: per-tile list counts, head bitmaps (run_ws_words)
-  // Sharded loop only (nullptr otherwise): every survivor a merge rewrote is appended to dlist
-  // (ctr->n_delta entries, any order, each slot once); mark[slot] == stamp dedupes the kernels
-  // that merge in place (stamp: unique per iteration, never reused by a context).
-  uint32_t* dlist;
-  uint32_t* mark;
-  uint32_t stamp;
-  // Size classes run concurrently on kMergeStreams auxiliary streams (fork after the run
-  // classification, join before the compaction): in the late, small iterations each class kernel
-  // is one long sequential walk, and serialised walks would add up.  aux[0] == nullptr: one stream.
-  // 385..896-row runs on aux 2 instead of ahead of the >896-row runs on the main stream: set by
-  // the engine when the previous iteration had many of them (C4: thousands; C2: < 10)
-  uint32_t big896_aux;
-  // >896-row runs: the launch's workgroup cap (0 = one per 897 positions, at most 512).  The
-  // engine sets a cap of 64 after an iteration without such runs: an empty launch of hundreds of
-  // 512-lane workgroups waits for CUs behind the other classes (C2: 25 ms per step of span)
-  uint32_t huge_cap;
-  // 1: no k_merge_huge launch; the 385..896-row kernel's workgroups walk the >896-row list after
-  // their own (set after several iterations without such runs: C2 and C5 never have any, and an
-  // empty launch still costs its dispatch; C4, where they recur, keeps the 512-lane kernel)
-  uint32_t huge_fold;
+  uint2* big[kBigClasses];    // (start, length) of runs for k_merge_big, per class
+  uint2 *huge, *over;         // ... for k_merge_huge; of oversize runs
+  RunCounters* rc;            // the run counts of this iteration
   // runs over 896 rows at d = 16 / 32 (k_merge_long): each workgroup's bit matrix, kLongRows x
-  // kLongRows / 64 words, and the number of workgroups it has room for (0: k_merge_huge)
+  // kLongRows / 64 words (nullptr: k_merge_huge)
   uint64_t* long_P;
-  uint32_t long_groups;
-  // option "long_runs": 4 (default) = k_merge_long also takes the 385..896-row runs, 1 = only
-  // the longer ones, 0 = k_merge_huge for those (long_off = 1)
+};
+// Sharded loop only (dlist == nullptr otherwise): every survivor a merge rewrote is appended to
+// dlist (ctr->n_delta entries, any order, each slot once); mark[slot] == stamp dedupes the kernels
+// that merge in place (stamp: unique per iteration, never reused by a context).
+struct DeltaSink { uint32_t *dlist, *mark; uint32_t stamp; };
+constexpr DeltaSink kNoSink{nullptr, nullptr, 0u};
+// k_merge_tail's 65..384-row runs screened first ("tail_big_screen"): the test's threshold, margins
+struct BigScreen { uint32_t on; float s_star, m0, a2; };
+// What a merge kernel takes: built by the launch code for one launch, const afterwards.
+struct MergeView : RunLists {
+  DeltaSink sink;
+  KTime kt;            // per-class stamps of this iteration's merge launches
+  uint32_t screened;   // 1: the small-run merge reads act instead of cls
+  uint32_t huge_fold;  // 1: the 385..896-row kernel's workgroups also walk the >896-row list
+  BigScreen bs;
+};
+static_assert(std::is_trivially_copyable<MergeView>::value, "a kernel argument");
+static_assert(sizeof(MergeView) == 232, "the merge kernels' argument block (DESIGN.md §3)");
+
+constexpr int kMergeStreams = 3;
+// The host's side (klsh_ctx::mp): the buffers reserve() allocates, the options, the loop's policy
+// for the next iteration, the streams.  Never a kernel argument.
+struct MergePlan {
+  RunLists lists;
+  uint32_t *tile_sums, *run_ws;  // run_ws: per-tile list counts, head bitmaps (run_ws_words)
+  uint32_t long_groups;  // the workgroups long_P has room for (0: k_merge_huge)
+  // ---- options (klsh_set_option; a launch size of 0 = the measured default, see the launch code)
+  // "long_runs": 4 (default) = k_merge_long also takes the 385..896-row runs, 1 = only the longer
+  // ones, 0 = k_merge_huge for those (long_off = 1)
   uint32_t long_off = 4;
-  // launch sizes (klsh_set_option; 0 = the measured default, see the launch code)
   uint32_t small_grid;       // "small_grid": the small-run merge's persistent launch
   uint32_t tail_nbig;        // "tail_big_groups": k_merge_tail's big-run workgroups
   uint32_t tail_nsmall;      // "tail_small_groups": k_merge_tail's small-run workgroups
@@ -174,26 +178,42 @@ struct MergeWork {
   // "tail_screen": 1 = the small-run screen also runs in front of k_merge_tail (iterations below
   // tail_merge_rows), whose small-run waves then walk only the runs it passed
   uint32_t tail_screen = 1;
-  // "tail_big_screen": 1 = there, k_merge_tail's 65..384-row runs are first screened on the fp16
-  // image in their workgroup (the small-run screen's certified test); a run with no pair left
-  // reads no f32 row.  big_screen / bs_*: set per launch (the test's threshold and margins).
+  // "tail_big_screen": 1 = there, the 65..384-row runs are first screened on the fp16 image in
+  // their workgroup (BigScreen); a run with no pair left reads no f32 row
   uint32_t tail_big_screen = 1;
-  uint32_t big_screen = 0;
-  float bs_s_star = 0.0f, bs_m0 = 0.0f, bs_a2 = 0.0f;
   uint32_t tail_screen_grid;  // "tail_screen_grid": its persistent launch there (0: 2048)
   // "tail_merge_rows": below this many positions every merge class runs in ONE launch
   // (k_merge_tail); 0 = the default 2^22 (tests lower it to reach the per-class launches)
   uint32_t tail_max;
-  // "grid_cap" (tests): at most this many workgroups for the per-class launches that stride over
-  // a run list (k_merge_big, k_merge_big_wide, k_merge_huge, k_merge_long); 0 = off
-  uint32_t grid_cap = 0;
-  hipStream_t aux[3];
-  KTime kt;                // per-class stamps of this iteration's merge launches
-  hipEvent_t small_ev[2];  // HIP events around the small-run launch (nullptr: not recorded)
-  hipEvent_t fork;
-  hipEvent_t join[3];
+  bool huge_fold_always = false;  // "huge_fold" (tests): fold in every iteration
+  // ---- the next iteration's launches, from the run counts of the last (klsh_loop.cpp)
+  // 385..896-row runs on aux 2 instead of ahead of the >896-row runs on the main stream: when the
+  // previous iteration had many of them (C4: thousands; C2: < 10)
+  uint32_t big896_aux;
+  // >896-row runs: the launch's workgroup cap (0 = one per 897 positions, at most 512).  64 after
+  // an iteration without such runs: an empty launch of hundreds of 512-lane workgroups waits for
+  // CUs behind the other classes (C2: 25 ms per step of span)
+  uint32_t huge_cap;
+  // 1: no k_merge_huge launch, MergeView::huge_fold instead (after several iterations without such
+  // runs: C2 and C5 never have any, an empty launch still costs its dispatch; C4 keeps the kernel)
+  uint32_t huge_fold;
+  uint32_t huge_quiet;  // consecutive iterations without >896-row runs
+  // no run counts yet (a call's start, klsh_pcluster)
+  void no_counts() { huge_cap = 0, huge_fold = huge_fold_always ? 1u : 0u; }
+  // Size classes run concurrently on kMergeStreams auxiliary streams (fork after the run
+  // classification, join before the compaction): in the late, small iterations each class kernel
+  // is one long sequential walk, and serialised walks would add up.  aux[0] == nullptr: one stream.
+  hipStream_t aux[kMergeStreams];
+  hipEvent_t fork, join[kMergeStreams];
 };
-constexpr int kMergeStreams = 3;
+// What one call of launch_merge / launch_runs / launch_tail_local adds.
+struct MergeCall {
+  KTime kt = kNoTime;                           // the iteration's stamps
+  hipEvent_t small_ev[2] = {nullptr, nullptr};  // HIP events around the small-run launch
+  DeltaSink sink = kNoSink;
+  uint32_t grid_cap = 0;  // klsh_ctx::grid_cap: the per-class launches that stride over a run list
+  MergeCall with_kt(KTime k) const { MergeCall m = *this; m.kt = k; return m; }
+};
 // Option "grid_cap" (tests; 0 = off): g workgroups, at most `cap`.  Only for launches whose
 // workgroups stride over a list or an index range on their own; a kernel whose workgroups take
 // one tile each, or wait for one another, must keep its grid.
@@ -208,7 +228,7 @@ inline bool long_ok(int d) { return d == 16 || d == 32; }
 // (2^22 since round 5: with the small-run screen and the big-run prescreen inside it, the one
 // launch beat the four-stream fork/join down to 4M positions — C2, one box, interleaved: 2^20
 // 200.2, 2^21 196.5, 2^22 193.1, 2^23 ~= 2^22, 2^24 +1 ms per step)
-inline uint32_t tail_merge_max(const MergeWork& w) { return w.tail_max ? w.tail_max : (1u << 22); }
+inline uint32_t tail_merge_max(const MergePlan& p) { return p.tail_max ? p.tail_max : (1u << 22); }
 
 // Row state, structure-of-arrays, one entry per slot (a slot is a row of the loaded matrix;
 // a merge writes the consensus into the candidate's slot, cluster.cc:70-74).
@@ -254,19 +274,29 @@ Decider make_decider(float thr);
 
 // Workspace of the wide-row matrix-core projection: the (row, hyperplane) pairs its screen could
 // not call (fix[0 .. cap)), a counter and a done counter (ws[0], ws[1]) that the fix-up kernel
-// returns to zero.  Zeroed once at allocation.
-struct ProjectWork {
+// returns to zero.  Zeroed once at allocation.  ProjectView is what the kernels take, ProjectPlan
+// the host's side (klsh_ctx::pp): the context's workspace and the options.
+struct ProjectView {
   uint2* fix;
   uint32_t* ws;
   uint32_t cap;
+  uint32_t h16_cs;  // "h16_bound" = 0: the fp16 projection bounds by |x||w|, not sum |x_k||w_k|
+};
+static_assert(std::is_trivially_copyable<ProjectView>::value && sizeof(ProjectView) == 24,
+              "a kernel argument");
+struct ProjectPlan {
+  ProjectView v;  // the context's workspace (reserve) and "h16_bound"
   // launch sizes and test hooks (klsh_set_option; 0 = default)
   uint32_t h16_grid;   // "h16_grid": fp16-image projection workgroups, at most
   uint32_t wide_grid;  // "wide_grid": wide-row screen workgroups, at most
   uint32_t fix_grid;   // "fix_grid": wide-row fix-up workgroups
   uint32_t segcap;     // "h16_segcap" (tests): fix-up entries per fp16-projection workgroup
-  uint32_t variant;    // "projection": kProjAuto / kProjPacked / kProjScreen (set per launch)
+  uint32_t variant;    // "projection": kProjAuto / kProjPacked / kProjScreen
   uint32_t wide_rolled;  // "wide_unrolled" = 0: d = 512 through the generic wide screen
-  uint32_t h16_cs;     // "h16_bound" = 0: the fp16 projection bounds by |x||w|, not sum |x_k||w_k|
+  // the same options over a caller's workspace (klsh_hash_keys)
+  ProjectPlan over(uint2* f, uint32_t* w, uint32_t c) const {
+    return ProjectPlan{{f, w, c, v.h16_cs}, h16_grid, wide_grid, fix_grid, segcap, variant, wide_rolled};
+  }
 };
 // Projection variants (klsh_set_option "projection"): the default picks the certified
 // matrix-core screen where it exists (the fp16 row image at d = 16 / 32 / 64, bf16x3 above 64)
@@ -289,9 +319,9 @@ bool project_device_n_ok(int d);
 void launch_project_device_n(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_t n_max,
                              const float* W, const uint32_t* n_dev, hipStream_t s,
                              KTime kt = kNoTime, const uint32_t* woff_dev = nullptr,
-                             const ProjectWork* pw = nullptr);
+                             const ProjectPlan* pp = nullptr);
 
-// pw (may be null): the workspace that enables the matrix-core screens (the fp16 row image where
+// pp (may be null): the plan that enables the matrix-core screens (the fp16 row image where
 // r.xh is set, bf16x3 for d > 64).  Returns the kernel it launched (ProjKernel).
 enum ProjKernel : int { kPkNone = -1, kPkPacked = 0, kPkH16 = 1, kPkWide = 2 };
 // The kernel behind a ProjKernel (option "last_hash_variant"; mirrored in _native.py): the three
@@ -308,7 +338,7 @@ enum ProjVariant : int {
 // variant (may be null): receives the ProjVariant launched.
 int launch_project(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_t n,
                    const float* W, int h, uint32_t key_or, hipStream_t s,
-                   const ProjectWork* pw = nullptr, KTime kt = kNoTime, int* variant = nullptr);
+                   const ProjectPlan* pp = nullptr, KTime kt = kNoTime, int* variant = nullptr);
 
 // Stable LSD radix sort of (keys, vals)[0..n) on the low `bits` bits (klsh_sort.hip); ping-pong
 // buffers, *out_k/*out_v = the pair holding the result.  ws: sort_ws_words(n) words.
@@ -319,25 +349,25 @@ void radix_sort(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t
 
 // Greedy merge (p_cluster) over every bucket run of equal key in positions [lo, hi) of
 // (key, slots), in place: survivors first in each run, kInvalid after.  Runs longer than
-// bucket_thr (>= 0) are queued to w.over (start, length) and left untouched.
+// bucket_thr (>= 0) are queued to p.lists.over (start, length) and left untouched.
 // n_dev (may be null; lo == 0 and hi < 2^20 only): the position count is read on the device
 // (<= hi, which sizes the grids).
 // runs_ready: the run lists of [lo, hi) are already built (launch_tail_local).
 void launch_merge(const Rows& r, const uint32_t* key, uint32_t* slots, uint32_t lo, uint32_t hi,
-                  float thr, int bucket_thr, const MergeWork& w, Counters* ctr, hipStream_t s,
-                  const uint32_t* n_dev = nullptr, bool runs_ready = false);
+                  float thr, int bucket_thr, const MergePlan& p, const MergeCall& c, Counters* ctr,
+                  hipStream_t s, const uint32_t* n_dev = nullptr, bool runs_ready = false);
 
 // Small iterations (< 2^20 positions, keys of 10..19 bits): the stable bucket sort in two steps
 // that also builds the run lists.  radix_sort_top: the stable partition of (k0, v0) by the top
 // kTailTopBits of `bits` key bits into (k1, v1); returns the top buckets' sizes.
 // launch_tail_local: every top bucket of (k1, v1) sorted stably by its low bits - kTailTopBits
-// bits into (k0, v0), and its runs of 2+ equal keys listed into w (as launch_runs would).
+// bits into (k0, v0), and its runs of 2+ equal keys listed into p.lists (as launch_runs would).
 const uint32_t* radix_sort_top(const uint32_t* k0, const uint32_t* v0, uint32_t* k1, uint32_t* v1,
                                uint32_t n, int bits, uint32_t* ws, hipStream_t s, KTime kt,
                                const uint32_t* n_dev);
 void launch_tail_local(const uint32_t* kin, const uint32_t* vin, uint32_t* kout, uint32_t* vout,
-                       const uint32_t* dtot, int bits, int bucket_thr, const MergeWork& w,
-                       hipStream_t s);
+                       const uint32_t* dtot, int bits, int bucket_thr, const MergePlan& p,
+                       const MergeCall& c, hipStream_t s);
 // the top-bits partition's digit width: 9 (512 top buckets of ~1K keys at C2's tail; the local
 // sorts then take up to 10 low bits) measured C2 188.0-188.7 -> 186.1-186.4 ms against 10 (one box,
 // interleaved, three rounds: the run listing 19.8 -> 18.3 ms per step, half the workgroups and
@@ -352,11 +382,11 @@ inline bool tail_local_ok(uint32_t n_max, int bits) {
 }
 
 // Bucket runs of positions [lo, lo + n) of sorted keys (n_dev: the count read on the device, as
-// launch_merge): every run of 2+ equal keys into its list of w (size classes, big classes, huge,
-// oversize), the counts into w.rc.  (launch_merge's first step; klsh_bucket_runs for tests.)
+// launch_merge): every run of 2+ equal keys into its list of p.lists (size classes, big classes,
+// huge, oversize), the counts into its rc. (launch_merge's first step; klsh_bucket_runs for tests.)
 constexpr int kRunListCount = kGroupClasses + kBigClasses + 2;
-void launch_runs(const uint32_t* key, uint32_t lo, uint32_t n, int bucket_thr, const MergeWork& w,
-                 hipStream_t s, const uint32_t* n_dev = nullptr);
+void launch_runs(const uint32_t* key, uint32_t lo, uint32_t n, int bucket_thr, const MergePlan& p,
+                 const MergeCall& c, hipStream_t s, const uint32_t* n_dev = nullptr);
 
 // Counters handed to the host through mapped pinned memory (no copy launch, no stream sync): the
 // compaction's last workgroup writes *ctr (total filled in) to `host`, zeroes *ctr for the next

@@ -340,7 +340,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
                                                      uint32_t* __restrict__ keys, uint32_t n,
                                                      const float* __restrict__ W, int h,
                                                      uint32_t key_or, float eps, float abs_c,
-                                                     ProjectWork pw, uint32_t segcap, KTime kt,
+                                                     ProjectView pw, uint32_t segcap, KTime kt,
                                                      const uint32_t* __restrict__ n_dev,
                                                      const uint32_t* __restrict__ woff_dev) {
   constexpr int KS = D / 16;  // k-steps of 16 columns
@@ -624,7 +624,7 @@ __global__ __launch_bounds__(kWideNT, 2) void k_project_mfma_wide(const float* _
                                                            uint32_t* __restrict__ keys, uint32_t n,
                                                            const float* __restrict__ W, int h,
                                                            uint32_t key_or, float eps, float abs_c,
-                                                           ProjectWork pw, KTime kt) {
+                                                           ProjectView pw, KTime kt) {
   extern __shared__ __attribute__((aligned(16))) unsigned char psm[];
   kt_fold(kt);
   kt_begin(kt, KC_PROJECT);
@@ -847,7 +847,7 @@ __global__ __launch_bounds__(256) void k_project_fix(const float* __restrict__ X
                                                      const uint32_t* __restrict__ slots,
                                                      uint32_t* __restrict__ keys,
                                                      const float* __restrict__ W, int h,
-                                                     ProjectWork pw, KTime kt,
+                                                     ProjectView pw, KTime kt,
                                                      const uint32_t* __restrict__ n_dev = nullptr,
                                                      const uint32_t* __restrict__ woff_dev = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float fw[];  // the h hyperplanes, stride dp
@@ -916,12 +916,12 @@ __global__ __launch_bounds__(256) void k_project_fix(const float* __restrict__ X
 // given) ignored: the kernel derives it from the device count.
 static void launch_h16(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_t n,
                        const float* W, int h, uint32_t key_or, hipStream_t s,
-                       const ProjectWork& pw, KTime kt, const uint32_t* n_dev,
-                       const uint32_t* woff_dev) {
-  const uint32_t gmax = pw.h16_grid ? pw.h16_grid : kH16Grid;  // "h16_grid"
+                       const ProjectPlan& pp, const ProjectView& pw, KTime kt,
+                       const uint32_t* n_dev, const uint32_t* woff_dev) {
+  const uint32_t gmax = pp.h16_grid ? pp.h16_grid : kH16Grid;  // "h16_grid"
   const uint32_t grid = std::min<uint32_t>((n + 255) / 256, gmax);
   uint32_t segcap = (pw.cap / 2) / grid;  // 16-B fix-up entries per workgroup
-  if (pw.segcap) segcap = std::min(segcap, pw.segcap);  // "h16_segcap" (tests: the in-place path)
+  if (pp.segcap) segcap = std::min(segcap, pp.segcap);  // "h16_segcap" (tests: the in-place path)
   const float eps = pw.h16_cs ? h16_eps(r.d) : h16_eps_t(r.d), abs_c = h16_abs(r.d);
   auto go = [&](auto screen) {
     screen<<<grid, 256, 0, s>>>(r.xh, r.x, r.dp, slots, keys, n, W, h, key_or, eps, abs_c, pw,
@@ -932,8 +932,8 @@ static void launch_h16(const Rows& r, const uint32_t* slots, uint32_t* keys, uin
   else go(k_project_h16<16>);
 }
 
-static bool h16_ok(const Rows& r, const ProjectWork* pw) {
-  return pw && pw->variant != kProjPacked && r.xh && (r.d == 16 || r.d == 32 || r.d == 64);
+static bool h16_ok(const Rows& r, const ProjectPlan* pp) {
+  return pp && pp->variant != kProjPacked && r.xh && (r.d == 16 || r.d == 32 || r.d == 64);
 }
 
 bool project_device_n_ok(int d) {
@@ -942,11 +942,11 @@ bool project_device_n_ok(int d) {
 
 void launch_project_device_n(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_t n_max,
                              const float* W, const uint32_t* n_dev, hipStream_t s, KTime kt,
-                             const uint32_t* woff_dev, const ProjectWork* pw) {
+                             const uint32_t* woff_dev, const ProjectPlan* pp) {
   if (n_max == 0) return;
-  if (h16_ok(r, pw)) {
+  if (h16_ok(r, pp)) {
     const int hmax = 31 - __builtin_clz(n_max);  // h of the device count is <= this
-    launch_h16(r, slots, keys, n_max, W, hmax, 0u, s, *pw, kt, n_dev, woff_dev);
+    launch_h16(r, slots, keys, n_max, W, hmax, 0u, s, *pp, pp->v, kt, n_dev, woff_dev);
     return;
   }
   const dim3 grid((n_max + 255) / 256), block(256);
@@ -966,14 +966,14 @@ void launch_project_device_n(const Rows& r, const uint32_t* slots, uint32_t* key
 // VALU chains (d = 8 and any d without a screen, or option "projection" = kProjPacked): the
 // wide-row packed kernel with the hyperplanes in LDS, else the generic kernel.
 int launch_project(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_t n,
-                    const float* W, int h, uint32_t key_or, hipStream_t s, const ProjectWork* pw,
+                    const float* W, int h, uint32_t key_or, hipStream_t s, const ProjectPlan* pp,
                     KTime kt, int* variant) {
   int pv_unused;
   int& pv = variant ? *variant : pv_unused;
   pv = kPvNone;
   if (n == 0) return kPkNone;
   const dim3 grid((n + 255) / 256), block(256);
-  if (pw && pw->variant != kProjPacked && r.d > 64 && h > 0) {
+  if (pp && pp->variant != kProjPacked && r.d > 64 && h > 0) {
     const size_t lds = (size_t)((r.d + 15) / 16) * 64 * 2 * 16 + 32 * sizeof(float);
     const size_t flds = sizeof(float) * (size_t)h * r.dp;  // the fix-up kernel's hyperplanes
     if (lds <= 96 * 1024 && flds <= 128 * 1024) {
@@ -989,27 +989,26 @@ int launch_project(const Rows& r, const uint32_t* slots, uint32_t* keys, uint32_
       // option "wide_grid": one resident round (2 workgroups of 6 waves per CU): C5 projection
       // 1203 -> 1076 ms per step (256..8192 swept on one box: 256 -> 1073, 512 -> 1076, 1024 ->
       // 1112, 2048 -> 1203, 4096 -> 1318, 8192 -> 1533)
-      const uint32_t wcap = pw->wide_grid ? pw->wide_grid : 512u;
+      const uint32_t wcap = pp->wide_grid ? pp->wide_grid : 512u;
       const dim3 gm(std::min<uint32_t>(groups, wcap));
       // stamped as one span: the screen (start) and the fix-up of its close calls (end)
-      KTime k1 = kt;
-      k1.fold = -1;
-      pv = r.d == 512 && !pw->wide_rolled ? kPvMfmaWide512 : kPvMfmaWide;
-      if (r.d == 512 && !pw->wide_rolled)  // option "wide_unrolled" (default 1)
+      const KTime k1 = kt.with_fold(-1);
+      pv = r.d == 512 && !pp->wide_rolled ? kPvMfmaWide512 : kPvMfmaWide;
+      if (r.d == 512 && !pp->wide_rolled)  // option "wide_unrolled" (default 1)
         k_project_mfma_wide<512><<<gm, dim3(kWideNT), lds, s>>>(r.x, r.d, r.dp, slots, keys, n, W,
                                                                 h, key_or, wide_eps(r.d),
-                                                                wide_abs(r.d), *pw, kt);
+                                                                wide_abs(r.d), pp->v, kt);
       else
         k_project_mfma_wide<0><<<gm, dim3(kWideNT), lds, s>>>(r.x, r.d, r.dp, slots, keys, n, W, h,
                                                               key_or, wide_eps(r.d), wide_abs(r.d),
-                                                              *pw, kt);
-      const uint32_t fcap = pw->fix_grid ? pw->fix_grid : 1024u;  // "fix_grid"
-      k_project_fix<<<fcap, block, flds, s>>>(r.x, r.d, r.dp, slots, keys, W, h, *pw, k1);
+                                                              pp->v, kt);
+      const uint32_t fcap = pp->fix_grid ? pp->fix_grid : 1024u;  // "fix_grid"
+      k_project_fix<<<fcap, block, flds, s>>>(r.x, r.d, r.dp, slots, keys, W, h, pp->v, k1);
       return kPkWide;
     }
   }
-  if (h16_ok(r, pw) && h > 0) {
-    launch_h16(r, slots, keys, n, W, h, key_or, s, *pw, kt, nullptr, nullptr);
+  if (h16_ok(r, pp) && h > 0) {
+    launch_h16(r, slots, keys, n, W, h, key_or, s, *pp, pp->v, kt, nullptr, nullptr);
     pv = kPvH16;
     return kPkH16;
   }

@@ -153,18 +153,16 @@ static inline void diag_log_batched(int, uint64_t, int, const Counters&) {}
 
 int merge_main(klsh_ctx* ctx, uint32_t* fk, uint32_t* fv, uint32_t n, float thr, int bucket_thr,
                uint32_t* out, klsh_stats* st, bool timed, bool sync,
-               const std::function<int(uint32_t*)>* after, KTime kt) {
+               const std::function<int(uint32_t*)>* after, KTime kt, const DeltaSink& sink) {
   hipStream_t s = ctx->stream;
   if (timed) KLSH_HIP(hipEventRecord(ctx->ev[EV_MERGE_BEGIN], s));
   // the small-run merge is a launch of its own at >= 2^20 positions (register widths): its HIP
   // events are the headline's cross-check
   const bool time_small = (ctx->hip_events || ctx->phase_timing) && kt.blk && st && sync &&
-                          n >= tail_merge_max(ctx->mw) && project_device_n_ok(ctx->d);
-  {
-    LaunchScope launch(ctx->mw, kt, time_small ? ctx->sev[0] : nullptr,
-                       time_small ? ctx->sev[1] : nullptr);
-    launch_merge(ctx->rows, fk, fv, 0, n, thr, bucket_thr, ctx->mw, ctx->ctr, s);
-  }
+                          n >= tail_merge_max(ctx->mp) && project_device_n_ok(ctx->d);
+  const MergeCall call{kt, {time_small ? ctx->sev[0] : nullptr, time_small ? ctx->sev[1] : nullptr},
+                       sink, ctx->grid_cap};
+  launch_merge(ctx->rows, fk, fv, 0, n, thr, bucket_thr, ctx->mp, call, ctx->ctr, s);
   KLSH_HIP(hipGetLastError());
   if (timed) KLSH_HIP(hipEventRecord(ctx->ev[EV_MERGE_END], s));
   const bool zc = sync && ctx->zero_copy;
@@ -184,7 +182,7 @@ int merge_main(klsh_ctx* ctx, uint32_t* fk, uint32_t* fv, uint32_t n, float thr,
     if (int e = ctx->sync_counters()) return e;
   }
   if (kt.blk && st) {  // this iteration's rows per kernel class
-    const bool tail = n < tail_merge_max(ctx->mw) && project_device_n_ok(ctx->d);
+    const bool tail = n < tail_merge_max(ctx->mp) && project_device_n_ok(ctx->d);
     count_class_rows(st, *ctx->h_ctr, n, tail);
   }
   if (time_small) {  // the compaction (published) runs after the merge streams' join
@@ -207,7 +205,7 @@ int oversize_runs(klsh_ctx* ctx, std::vector<uint2>* over, uint64_t* hyperplanes
   over->resize(n_over);
   *hyperplanes = 0;
   if (n_over == 0) return 0;
-  KLSH_HIP(hipMemcpy(over->data(), ctx->mw.over, sizeof(uint2) * n_over, hipMemcpyDeviceToHost));
+  KLSH_HIP(hipMemcpy(over->data(), ctx->mp.lists.over, sizeof(uint2) * n_over, hipMemcpyDeviceToHost));
   std::sort(over->begin(), over->end(), [](const uint2& a, const uint2& b) { return a.x < b.x; });
   for (const uint2& o : *over) *hyperplanes += (uint64_t)floor_log2(o.y);
   return 0;
@@ -215,8 +213,9 @@ int oversize_runs(klsh_ctx* ctx, std::vector<uint2>* over, uint64_t* hyperplanes
 
 int merge_nested(klsh_ctx* ctx, uint32_t* fk, uint32_t* fv, uint32_t n, float thr,
                  const std::vector<uint2>& over, uint32_t seed_base, uint64_t* rng_counter,
-                 uint32_t* out, klsh_stats* st) {
+                 uint32_t* out, klsh_stats* st, const DeltaSink& sink) {
   hipStream_t s = ctx->stream;
+  const MergeCall call{kNoTime, {nullptr, nullptr}, sink, ctx->grid_cap};
   for (uint32_t oi = 0; oi < (uint32_t)over.size(); ++oi) {
     const uint32_t p = over[oi].x, b = over[oi].y;
     const int h2 = floor_log2(b);
@@ -231,14 +230,14 @@ int merge_nested(klsh_ctx* ctx, uint32_t* fk, uint32_t* fv, uint32_t n, float th
     // Sub-keys carry bit 31 (main keys are < 2^h <= 2^31, so never have it) and a bit 30 that
     // alternates between consecutive oversize regions, so no run crosses a region boundary.
     const uint32_t key_or = 0x80000000u | ((oi & 1u) << 30);
-    launch_project(ctx->rows, fv + p, ctx->nk1, b, ctx->hyperplane_ptr(k), h2, key_or, s, &ctx->pw);
+    launch_project(ctx->rows, fv + p, ctx->nk1, b, ctx->hyperplane_ptr(k), h2, key_or, s, &ctx->pp);
     uint32_t *rk = nullptr, *rv = nullptr;
     radix_sort(ctx->nk1, fv + p, ctx->nk2, ctx->nv2, b, h2, ctx->hist, &rk, &rv, s);
     KLSH_HIP(hipMemcpyAsync(fk + p, rk, 4ull * b, hipMemcpyDeviceToDevice, s));
     if (rv != fv + p) KLSH_HIP(hipMemcpyAsync(fv + p, rv, 4ull * b, hipMemcpyDeviceToDevice, s));
     // fresh run lists for the region
     KLSH_HIP(hipMemsetAsync(ctx->rc, 0, sizeof(RunCounters), s));
-    launch_merge(ctx->rows, fk, fv, p, p + b, thr, -1, ctx->mw, ctx->ctr, s);
+    launch_merge(ctx->rows, fk, fv, p, p + b, thr, -1, ctx->mp, call, ctx->ctr, s);
     KLSH_HIP(hipGetLastError());
   }
   launch_compact(fv, n, out, ctx->tile_sums, ctx->ctr, s, nullptr, ctx->rc);
@@ -252,16 +251,13 @@ int merge_and_compact(klsh_ctx* ctx, uint32_t* fk, uint32_t* fv, uint32_t n, flo
   uint32_t* out = (fv == ctx->order) ? ctx->alt : ctx->order;
   if (int e = merge_main(ctx, fk, fv, n, thr, bucket_thr, out, st, timed, true, after, kt))
     return e;
-  // many 385..896-row runs this iteration: the next one runs that class on an auxiliary stream
-  ctx->mw.big896_aux = ctx->h_ctr->n_big[kBigClasses - 1] >= 64u ? 1u : 0u;
-  // no >896-row runs this iteration: the next one's launch for them is 64 workgroups (C4 has
-  // iterations without them between ones with dozens: a cap of 4 serialised those walks,
-  // k_merge_huge<32> 746 -> 1024 ms per step)
-  ctx->mw.huge_cap = ctx->h_ctr->n_huge == 0 ? 64u : 0u;
-  // several iterations in a row without them: the next one walks any >896-row runs inside the
-  // 385..896-row kernel instead of launching k_merge_huge (an empty launch on C2 / C5)
-  ctx->huge_quiet = ctx->h_ctr->n_huge == 0 ? ctx->huge_quiet + 1 : 0;
-  ctx->mw.huge_fold = (ctx->huge_quiet >= 4 || ctx->huge_fold_always) ? 1u : 0u;
+  MergePlan& mp = ctx->mp;  // the next iteration's long-run launches, from this one's run counts
+  mp.big896_aux = ctx->h_ctr->n_big[kBigClasses - 1] >= 64u ? 1u : 0u;
+  // (C4 has iterations without >896-row runs between ones with dozens: a cap of 4 serialised
+  // those walks, k_merge_huge<32> 746 -> 1024 ms per step)
+  mp.huge_cap = ctx->h_ctr->n_huge == 0 ? 64u : 0u;
+  mp.huge_quiet = ctx->h_ctr->n_huge == 0 ? mp.huge_quiet + 1 : 0;
+  mp.huge_fold = (mp.huge_quiet >= 4 || mp.huge_fold_always) ? 1u : 0u;
   if (ctx->h_ctr->n_over > 0) {
     std::vector<uint2> over;
     uint64_t hyp = 0;
@@ -286,12 +282,12 @@ int merge_and_compact(klsh_ctx* ctx, uint32_t* fk, uint32_t* fv, uint32_t n, flo
 // the RNG counter and the statistics come out exactly as the per-iteration loop's.
 static bool batch_eligible(const klsh_ctx* ctx, uint64_t n, int bucket_thr, int iters_left) {
   // (< 2^20 too: the queued compaction is the one-launch look-back over <= 256 tiles)
-  if (!ctx->tail_batch || n < 2 || n >= std::min<uint64_t>(tail_merge_max(ctx->mw), 1u << 20) ||
+  if (!ctx->tail_batch || n < 2 || n >= std::min<uint64_t>(tail_merge_max(ctx->mp), 1u << 20) ||
       iters_left < 2)
     return false;
   if (bucket_thr >= 0 && n > (uint64_t)bucket_thr) return false;
   if (!ctx->zero_copy || !ctx->ring_dev || !ctx->lb.status || ctx->phase_timing) return false;
-  if (!project_device_n_ok(ctx->d) || ctx->mw.dlist) return false;
+  if (!project_device_n_ok(ctx->d) || ctx->shards(n)) return false;
   if (diag_host_driven()) return false;
   // every queued iteration's hyperplanes resident at once
   return (uint64_t)iters_left * (uint64_t)floor_log2(n) * (uint64_t)ctx->dp <= (64ull << 20);
@@ -344,24 +340,24 @@ static int run_batched(klsh_ctx* ctx, float& threshold, float sim_step, int it, 
       const KTime kt = ktime(ctx->kt_iter++);
       if (!queued)
         launch_project_device_n(ctx->rows, ctx->order, ctx->keys, (uint32_t)n_max, ctx->W, n_dev, s,
-                                kt, woff_dev, &ctx->pw);
+                                kt, woff_dev, &ctx->pp);
       queued = false;
       uint32_t *fk = nullptr, *fv = nullptr;
       const bool local = ctx->tail_local && tail_local_ok((uint32_t)n_max, hb);
-      LaunchScope launch(ctx->mw, kt);  // (the sorts do not read it)
+      const MergeCall call{kt, {nullptr, nullptr}, kNoSink, ctx->grid_cap};
       if (local) {  // top-bits partition, then the buckets sorted in LDS with their runs listed
         const uint32_t* dtot = radix_sort_top(ctx->keys, ctx->order, ctx->keys2, ctx->alt,
                                               (uint32_t)n_max, hb, ctx->hist, s, kt, n_dev);
         launch_tail_local(ctx->keys2, ctx->alt, ctx->keys, ctx->order, dtot, hb,
-                          bucket_size_threshold, ctx->mw, s);
+                          bucket_size_threshold, ctx->mp, call, s);
         fk = ctx->keys;
         fv = ctx->order;
       } else {
         radix_sort(ctx->keys, ctx->order, ctx->keys2, ctx->alt, (uint32_t)n_max, hb, ctx->hist,
                    &fk, &fv, s, kt, n_dev);
       }
-      launch_merge(ctx->rows, fk, fv, 0, (uint32_t)n_max, thr, bucket_size_threshold, ctx->mw,
-                   ctx->ctr, s, n_dev, local);
+      launch_merge(ctx->rows, fk, fv, 0, (uint32_t)n_max, thr, bucket_size_threshold, ctx->mp,
+                   call, ctx->ctr, s, n_dev, local);
       uint32_t* out = (fv == ctx->order) ? ctx->alt : ctx->order;
       Publish pub{ctx->ring_dev + slot, ctx->pub_seq_dev, ++ctx->pub_seq, n_dev, woff_dev};
       launch_compact(fv, (uint32_t)n_max, out, ctx->tile_sums, ctx->ctr, s, &pub, ctx->rc, kt,
@@ -459,7 +455,7 @@ int run_single(klsh_ctx* ctx, float& threshold, float sim_step, int it_begin, in
       if (!ctx->ctr_clean) if (int e = ctx->reset_counters()) return e;
       if (rec) KLSH_HIP(hipEventRecord(ctx->project_begin(pair), s));
       launch_project(ctx->rows, ctx->order, ctx->keys, (uint32_t)n, ctx->hyperplane_ptr(k), h, 0u,
-                     s, &ctx->pw, ktime(j));
+                     s, &ctx->pp, ktime(j));
       KLSH_HIP(hipGetLastError());
       if (rec) KLSH_HIP(hipEventRecord(ctx->project_end(pair), s));
     }
@@ -485,7 +481,7 @@ int run_single(klsh_ctx* ctx, float& threshold, float sim_step, int it_begin, in
       if (rec) KLSH_HIP(hipEventRecord(ctx->project_begin(next_pair), s));
       launch_project_device_n(ctx->rows, next_order, spec_out, (uint32_t)n,
                               ctx->hyperplane_ptr(k_next), ctx->n_next_dev, s, ktime(j + 1),
-                              nullptr, &ctx->pw);
+                              nullptr, &ctx->pp);
       KLSH_HIP(hipGetLastError());
       if (rec) KLSH_HIP(hipEventRecord(ctx->project_end(next_pair), s));
       ctx->spec = QueuedProjection{true, k_next, next_pair, spec_out == ctx->keys2};
@@ -542,9 +538,7 @@ extern "C" int klsh_cluster(klsh_ctx* ctx, float min_similarity, int iterations,
   memset(st, 0, sizeof(*st));
   st->struct_size = sizeof(*st);
   st->world = (uint64_t)ctx->world();
-  ctx->mw.huge_cap = 0;  // (set per iteration from the run counts by the single-device loop)
-  ctx->mw.huge_fold = ctx->huge_fold_always ? 1u : 0u;
-  ctx->huge_quiet = 0;
+  ctx->mp.no_counts(), ctx->mp.huge_quiet = 0;  // (the single-device loop sets it per iteration)
   const int run_iters = ctx->stop_after > 0 ? std::min(iterations, ctx->stop_after) : iterations;
   if (ctx->comm)  // any bound group, world 1 included (measures the sharded machinery alone)
     return cluster_sharded(ctx, min_similarity, iterations, run_iters, bucket_size_threshold,
@@ -559,7 +553,7 @@ extern "C" int klsh_cluster(klsh_ctx* ctx, float min_similarity, int iterations,
   ctx->ctr_clean = false;
   ctx->drop_queued_projection();
   // no run counts yet: only very large inputs start with the 385..896-row class on aux 2
-  ctx->mw.big896_aux = ctx->n_live >= (1u << 24) ? 1u : 0u;
+  ctx->mp.big896_aux = ctx->n_live >= (1u << 24) ? 1u : 0u;
   // Every call draws its hyperplanes afresh (the reference draws them inside Cluster(),
   // lshash.cc:36-42), so repeated timed calls never reuse a previous call's tables.
   ctx->w_count = 0;
@@ -578,11 +572,11 @@ extern "C" int klsh_cluster(klsh_ctx* ctx, float min_similarity, int iterations,
   // The survivor counters are published by the compaction's last workgroup, which need not be
   // the last to finish writing ctx->order: drain the stream before klsh_count/klsh_result read it.
   KLSH_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->pw.ws) {  // pairs the certified projection screens left to the exact chains
+  if (ctx->pp.v.ws) {  // pairs the certified projection screens left to the exact chains
     uint32_t w[64];
-    KLSH_HIP(hipMemcpy(w, ctx->pw.ws, sizeof(w), hipMemcpyDeviceToHost));
-    KLSH_HIP(hipMemset(ctx->pw.ws + 4, 0, 8));
-    KLSH_HIP(hipMemset(ctx->pw.ws + 32, 0, 128));
+    KLSH_HIP(hipMemcpy(w, ctx->pp.v.ws, sizeof(w), hipMemcpyDeviceToHost));
+    KLSH_HIP(hipMemset(ctx->pp.v.ws + 4, 0, 8));
+    KLSH_HIP(hipMemset(ctx->pp.v.ws + 32, 0, 128));
     st->proj_fix_pairs = proj_close_pairs(w);
   }
   st->n_final = ctx->n_live;

@@ -8,28 +8,6 @@
 
 namespace klsh {
 
-// The per-launch fields of MergeWork, set for the launches inside one scope and cleared when it
-// ends, however it ends: the iteration's stamps and the event pair around the small-run merge.
-struct LaunchScope {
-  MergeWork& mw;
-  LaunchScope(MergeWork& w, KTime kt, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) : mw(w) {
-    mw.kt = kt, mw.small_ev[0] = e0, mw.small_ev[1] = e1;
-  }
-  ~LaunchScope() { mw.kt = kNoTime, mw.small_ev[0] = mw.small_ev[1] = nullptr; }
-  LaunchScope(const LaunchScope&) = delete;
-};
-
-// Sharded loop: while the scope lives, the merge kernels list the survivors they rewrite
-// (MergeWork::dlist, deduplicated through mark / stamp).
-struct DeltaScope {
-  MergeWork& mw;
-  DeltaScope(MergeWork& w, uint32_t* dlist, uint32_t* mark, uint32_t stamp) : mw(w) {
-    mw.dlist = dlist, mw.mark = mark, mw.stamp = stamp;
-  }
-  ~DeltaScope() { mw.dlist = mw.mark = nullptr; }
-  DeltaScope(const DeltaScope&) = delete;
-};
-
 // One finished iteration over n rows with h hyperplanes that left n_next (n = 0: the reference
 // aborts on an empty vector, here the iteration only counts).
 inline void account_iteration(klsh_stats* st, uint64_t n, int h, uint64_t n_next) {
@@ -43,12 +21,13 @@ inline void account_iteration(klsh_stats* st, uint64_t n, int h, uint64_t n_next
 }
 
 // Merge + compaction of one iteration's sorted runs (fk/fv, n positions, in place on fv) into
-// `out` (inside a DeltaScope the merge kernels also list the survivors they rewrote).
-// Ends with the counters on the host: total (survivors), n_over (oversize runs), n_delta.
-// kt: the iteration's stamps (kNoTime: untimed).
+// `out`.  Ends with the counters on the host: total (survivors), n_over (oversize runs), n_delta.
+// kt: the iteration's stamps (kNoTime: untimed).  sink (sharded loop): where the merge kernels
+// list the survivors they rewrote.
 int merge_main(klsh_ctx* ctx, uint32_t* fk, uint32_t* fv, uint32_t n, float thr, int bucket_thr,
                uint32_t* out, klsh_stats* st, bool timed, bool sync = true,
-               const std::function<int(uint32_t*)>* after = nullptr, KTime kt = kNoTime);
+               const std::function<int(uint32_t*)>* after = nullptr, KTime kt = kNoTime,
+               const DeltaSink& sink = kNoSink);
 // The oversize runs of the last merge_main, ascending (the reference's T=1 order):
 // (start, length) pairs and the hyperplanes their nestedCluster calls draw (floor(log2 b) each).
 int oversize_runs(klsh_ctx* ctx, std::vector<uint2>* over, uint64_t* hyperplanes);
@@ -57,7 +36,7 @@ int oversize_runs(klsh_ctx* ctx, std::vector<uint2>* over, uint64_t* hyperplanes
 // the counters on the host.
 int merge_nested(klsh_ctx* ctx, uint32_t* fk, uint32_t* fv, uint32_t n, float thr,
                  const std::vector<uint2>& over, uint32_t seed_base, uint64_t* rng_counter,
-                 uint32_t* out, klsh_stats* st);
+                 uint32_t* out, klsh_stats* st, const DeltaSink& sink = kNoSink);
 // Single-GPU: merge, compaction and nested buckets of one iteration.  fk/fv: sorted keys/slots
 // (fv is one of ctx->order / ctx->alt).  Returns with the new canonical order in ctx->order and
 // ctx->n_live updated.

@@ -86,7 +86,7 @@ static int cluster_sharded_body(klsh_ctx* ctx, float min_similarity, int iterati
 
   bool replicated = false;
   for (int it = 0; it < run_iters; ++it) {
-    if (N < ctx->shard_min_rows) {  // the replicated tail: every rank runs the rest on its own
+    if (!ctx->shards(N)) {  // the replicated tail: every rank runs the rest on its own
       if (int e = gather_order()) return e;
       ctx->n_live = N;
       replicated = true;
@@ -116,13 +116,13 @@ static int cluster_sharded_body(klsh_ctx* ctx, float min_similarity, int iterati
     const bool rec = ctx->hip_events || ctx->phase_timing;
     if (rec) KLSH_HIP(hipEventRecord(ctx->ev[EV_PROJECT_BEGIN], s));
     launch_project(ctx->rows, ctx->order, ctx->keys, n_g, ctx->hyperplane_ptr(k), h, 0u, s,
-                   &ctx->pw);
+                   &ctx->pp);
     KLSH_HIP(hipGetLastError());
     if (rec) KLSH_HIP(hipEventRecord(ctx->ev[EV_PROJECT_END], s));
     const int B = std::min(h, kMaxBinBits);
     const int shift = h - B;
     const uint32_t nbins = 1u << B;
-    launch_bin_hist(ctx->keys, n_g, shift, nbins, ctx->bins, s, ctx->mw.grid_cap);
+    launch_bin_hist(ctx->keys, n_g, shift, nbins, ctx->bins, s, ctx->grid_cap);
     if (timed_comm([&] { return cm->allgather(ctx->bins, ctx->bins_all, 4ull * nbins, s); }))
       return comm_fail("bin histogram allgather");
     launch_bin_split(ctx->bins_all, W, nbins, N, ctx->owner, ctx->cntmat, s);
@@ -165,9 +165,9 @@ static int cluster_sharded_body(klsh_ctx* ctx, float min_similarity, int iterati
     if (ctx->phase_timing) KLSH_HIP(hipEventRecord(ctx->ev[EV_SORT_END], s));
     uint32_t* out = (fv == ctx->order) ? ctx->alt : ctx->order;
     // the merge kernels of this iteration list the survivors they rewrite
-    DeltaScope delta(ctx->mw, ctx->dslots, ctx->mark, ++ctx->stamp);
+    const DeltaSink sink{ctx->dslots, ctx->mark, ++ctx->stamp};
     if (int e = merge_main(ctx, fk, fv, m_g, threshold, bucket_size_threshold, out, st,
-                           ctx->phase_timing, /*sync=*/false))
+                           ctx->phase_timing, /*sync=*/false, nullptr, kNoTime, sink))
       return e;
     // 4. counters of every rank in one exchange and one host sync: oversize runs, survivors,
     //    rewritten rows (n_over, total, n_delta are adjacent in Counters)
@@ -218,7 +218,8 @@ static int cluster_sharded_body(klsh_ctx* ctx, float min_similarity, int iterati
       }
       uint64_t rng = *rng_counter + hyp_before;
       if (!over.empty())
-        if (int e = merge_nested(ctx, fk, fv, m_g, threshold, over, seed_base, &rng, out, st))
+        if (int e = merge_nested(ctx, fk, fv, m_g, threshold, over, seed_base, &rng, out, st,
+                                     sink))
           return e;
       *rng_counter += hyp_all;
       if (int e = exchange_counters(ctx->h_ctr->total, ctx->h_ctr->n_delta, 0, 0)) return e;
@@ -238,12 +239,12 @@ static int cluster_sharded_body(klsh_ctx* ctx, float min_similarity, int iterati
     if (nd_all) {
       if (int e = ctx->reserve_words(&ctx->drec, &ctx->drec_cap, (size_t)R * ndel[g] + 1)) return e;
       if (int e = ctx->reserve_words(&ctx->drec_all, &ctx->drec_all_cap, (size_t)R * nd_all)) return e;
-      launch_delta_pack(ctx->rows, ctx->dslots, ndel[g], ctx->drec, s, ctx->mw.grid_cap);
+      launch_delta_pack(ctx->rows, ctx->dslots, ndel[g], ctx->drec, s, ctx->grid_cap);
       if (timed_comm([&] {
             return cm->allgatherv(ctx->drec, ctx->drec_all, dcnt.data(), doff.data(), s);
           }))
         return comm_fail("delta allgather");
-      launch_delta_apply(ctx->rows, ctx->drec_all, (uint32_t)nd_all, s, ctx->mw.grid_cap);
+      launch_delta_apply(ctx->rows, ctx->drec_all, (uint32_t)nd_all, s, ctx->grid_cap);
       KLSH_HIP(hipGetLastError());
     }
 

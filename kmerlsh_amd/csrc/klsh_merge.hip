@@ -99,89 +99,98 @@ static bool raise_lds_limit(size_t bytes, K*... kern) {
   return ok;
 }
 
-static void launch_huge(const MergeWork& w, uint32_t* slots, const Decider& dc, const Rows& r,
-                        Counters* ctr, uint32_t n, hipStream_t s) {
-  const bool with896 = long896(w, dc, r);
-  if (w.huge_fold && !with896) return;  // the 385..896-row kernel walks them (k_merge_big)
+// What one launch's kernels read: the plan's lists and fold policy, the call's sink and stamps,
+// and the launch's own flags.
+static MergeView view(const MergePlan& p, const MergeCall& c, uint32_t screened = 0u,
+                      BigScreen bs = BigScreen{0u, 0.0f, 0.0f, 0.0f}) {
+  return MergeView{p.lists, c.sink, c.kt, screened, p.huge_fold, bs};
+}
+
+static void launch_huge(const MergePlan& p, const MergeCall& c, uint32_t* slots, const Decider& dc,
+                        const Rows& r, Counters* ctr, uint32_t n, hipStream_t s) {
+  const bool with896 = long896(p, dc, r);
+  if (p.huge_fold && !with896) return;  // the 385..896-row kernel walks them (k_merge_big)
   uint32_t g = (uint32_t)std::min<uint64_t>(512, n / (kBigRows[kBigClasses - 1] + 1) + 1);
-  if (w.huge_cap && !with896) g = std::min(g, w.huge_cap);  // (the kernel strides over its list)
+  if (p.huge_cap && !with896) g = std::min(g, p.huge_cap);  // (the kernel strides over its list)
   if (with896) g = (uint32_t)std::min<uint64_t>(1024, n / (kBigRows[kBigClasses - 2] + 1) + 1);
-  if (long_ok_for(w, dc, r)) {
+  const RunLists& l = p.lists;
+  const MergeView w = view(p, c);
+  if (long_ok_for(p, dc, r)) {
     const size_t lds = std::max(long_lds(), huge_lds(r.d, r.dp, kLongNT));
     static const bool lds_ok = raise_lds_limit(lds, &k_merge_long<16>, &k_merge_long<32>);
     (void)lds_ok;
     // (the matrices stay sized for long_groups workgroups; "grid_cap" only leaves some unused)
-    g = cap_grid(std::min(g, w.long_groups), w.grid_cap);
-    const uint2* l2 = with896 ? w.big[kBigClasses - 1] : nullptr;
-    const uint32_t* c2 = &w.rc->n_big[kBigClasses - 1].v;
+    g = cap_grid(std::min(g, p.long_groups), c.grid_cap);
+    const uint2* l2 = with896 ? l.big[kBigClasses - 1] : nullptr;
+    const uint32_t* c2 = &l.rc->n_big[kBigClasses - 1].v;
     if (r.d == 16)
-      k_merge_long<16><<<g, kLongNT, lds, s>>>(w.huge, &w.rc->n_huge.v, l2, c2, slots, dc, r, w, ctr);
+      k_merge_long<16><<<g, kLongNT, lds, s>>>(l.huge, &l.rc->n_huge.v, l2, c2, slots, dc, r, w, ctr);
     else
-      k_merge_long<32><<<g, kLongNT, lds, s>>>(w.huge, &w.rc->n_huge.v, l2, c2, slots, dc, r, w, ctr);
+      k_merge_long<32><<<g, kLongNT, lds, s>>>(l.huge, &l.rc->n_huge.v, l2, c2, slots, dc, r, w, ctr);
     return;
   }
-  g = cap_grid(g, w.grid_cap);
+  g = cap_grid(g, c.grid_cap);
   const size_t lds = huge_lds(r.d, r.dp, kHugeNT);
   static const bool lds_ok =
       raise_lds_limit(96 * 1024, &k_merge_huge<0>, &k_merge_huge<8>, &k_merge_huge<16>,
                       &k_merge_huge<32>, &k_merge_huge<64>);
   (void)lds_ok;
   switch (r.d) {
-    case 8: k_merge_huge<8><<<g, kHugeNT, lds, s>>>(w.huge, &w.rc->n_huge.v, slots, dc, r, w, ctr); break;
-    case 16: k_merge_huge<16><<<g, kHugeNT, lds, s>>>(w.huge, &w.rc->n_huge.v, slots, dc, r, w, ctr); break;
-    case 32: k_merge_huge<32><<<g, kHugeNT, lds, s>>>(w.huge, &w.rc->n_huge.v, slots, dc, r, w, ctr); break;
-    case 64: k_merge_huge<64><<<g, kHugeNT, lds, s>>>(w.huge, &w.rc->n_huge.v, slots, dc, r, w, ctr); break;
-    default: k_merge_huge<0><<<g, kHugeNT, lds, s>>>(w.huge, &w.rc->n_huge.v, slots, dc, r, w, ctr);
+    case 8: k_merge_huge<8><<<g, kHugeNT, lds, s>>>(l.huge, &l.rc->n_huge.v, slots, dc, r, w, ctr); break;
+    case 16: k_merge_huge<16><<<g, kHugeNT, lds, s>>>(l.huge, &l.rc->n_huge.v, slots, dc, r, w, ctr); break;
+    case 32: k_merge_huge<32><<<g, kHugeNT, lds, s>>>(l.huge, &l.rc->n_huge.v, slots, dc, r, w, ctr); break;
+    case 64: k_merge_huge<64><<<g, kHugeNT, lds, s>>>(l.huge, &l.rc->n_huge.v, slots, dc, r, w, ctr); break;
+    default: k_merge_huge<0><<<g, kHugeNT, lds, s>>>(l.huge, &l.rc->n_huge.v, slots, dc, r, w, ctr);
   }
 }
 
 // One class c of 65..896-row runs, for k_merge_big and k_merge_big_wide (rb rows per run at the
 // most, nt lanes, `layout` bytes of LDS): a workgroup per run that n positions can hold at the
 // class's shortest length, up to 1024; the 385..896 class takes huge_runs' LDS too when it folds
-// the longer runs in (w.huge_fold).
+// the longer runs in (MergePlan::huge_fold).
 template <class Kern>
-static void launch_big_class(Kern kern, int rb, int nt, size_t layout, const MergeWork& w, int c,
-                             uint32_t* slots, const Decider& dc, const Rows& r, Counters* ctr,
-                             uint32_t n, hipStream_t s) {
-  const bool fold = rb == kBigRows[kBigClasses - 1] && w.huge_fold;
+static void launch_big_class(Kern kern, int rb, int nt, size_t layout, const MergePlan& p,
+                             const MergeCall& c, int cls, uint32_t* slots, const Decider& dc,
+                             const Rows& r, Counters* ctr, uint32_t n, hipStream_t s) {
+  const bool fold = rb == kBigRows[kBigClasses - 1] && p.huge_fold;
   const size_t lds = fold ? std::max(layout, huge_lds(r.d, r.dp, nt)) : layout;
-  const uint32_t lo = c == 0 ? 65u : (uint32_t)kBigRows[c - 1] + 1u;
-  const uint32_t g = cap_grid((uint32_t)std::min<uint64_t>(1024, n / lo + 1), w.grid_cap);
-  kern<<<g, nt, lds, s>>>(w, c, slots, dc, r, ctr);
+  const uint32_t lo = cls == 0 ? 65u : (uint32_t)kBigRows[cls - 1] + 1u;
+  const uint32_t g = cap_grid((uint32_t)std::min<uint64_t>(1024, n / lo + 1), c.grid_cap);
+  kern<<<g, nt, lds, s>>>(view(p, c), cls, slots, dc, r, ctr);
 }
 
 template <int D, int RB, int NT, bool ROWS_LDS>
-static void launch_big(const MergeWork& w, int c, uint32_t* slots, const Decider& dc, const Rows& r,
-                       Counters* ctr, uint32_t n, hipStream_t s) {  // (r.d == D: launch_merge)
-  using L = BigLayout<D, RB, ROWS_LDS>;
+static void launch_big(const MergePlan& p, const MergeCall& c, int cls, uint32_t* slots,
+                       const Decider& dc, const Rows& r, Counters* ctr, uint32_t n, hipStream_t s) {
+  using L = BigLayout<D, RB, ROWS_LDS>;  // (r.d == D: launch_merge)
   const auto kern = &k_merge_big<D, RB, NT, ROWS_LDS>;
   static const bool lds_ok = raise_lds_limit(std::max<size_t>(L::bytes, 96 * 1024), kern);
   (void)lds_ok;
-  launch_big_class(kern, RB, NT, L::bytes, w, c, slots, dc, r, ctr, n, s);
+  launch_big_class(kern, RB, NT, L::bytes, p, c, cls, slots, dc, r, ctr, n, s);
 }
 
 // Fork the size-class kernels onto the auxiliary streams (after k_runs on s) and join them back
 // into s.  Every class writes disjoint runs, so the order between classes is free.
 struct Fork {
-  const MergeWork& w;
+  const MergePlan& p;
   hipStream_t s;
   bool on;
-  Fork(const MergeWork& w_, hipStream_t s_) : w(w_), s(s_) {
+  Fork(const MergePlan& p_, hipStream_t s_) : p(p_), s(s_) {
 #ifdef KLSH_SERIAL_MERGE  // diagnostics build only: every class in order on the main stream
     on = false;
 #else
-    on = w.aux[0] != nullptr;
+    on = p.aux[0] != nullptr;
 #endif
     if (!on) return;
-    (void)hipEventRecord(w.fork, s);
-    for (int i = 0; i < kMergeStreams; ++i) (void)hipStreamWaitEvent(w.aux[i], w.fork, 0);
+    (void)hipEventRecord(p.fork, s);
+    for (int i = 0; i < kMergeStreams; ++i) (void)hipStreamWaitEvent(p.aux[i], p.fork, 0);
   }
-  hipStream_t lane(int i) const { return on ? w.aux[i] : s; }
+  hipStream_t lane(int i) const { return on ? p.aux[i] : s; }
   ~Fork() {
     if (!on) return;
     for (int i = 0; i < kMergeStreams; ++i) {
-      (void)hipEventRecord(w.join[i], w.aux[i]);
-      (void)hipStreamWaitEvent(s, w.join[i], 0);
+      (void)hipEventRecord(p.join[i], p.aux[i]);
+      (void)hipStreamWaitEvent(s, p.join[i], 0);
     }
   }
 };
@@ -199,22 +208,17 @@ static void screen_margins(int d, float* m0, float* a2) {
   *m0 = 1.5f * (0x1p-9f + 0x1p-20f + (4.0f * (float)d + 16.0f) * 0x1p-24f);
   *a2 = 1.5f * 2.0f * 0x1p-25f * std::sqrt((float)d);
 }
-static bool screen_ok(const Rows& r, const Decider& dc, const MergeWork& w) {
-  return w.small_screen && r.xh && dc.fast && (r.d == 32 || r.d == 64);  // (tiles: d >= 32)
-}
-
-// The small-run merge's persistent launch (option "small_grid"; default 12288).
-static uint32_t small_grid(const MergeWork& w) {
-  return w.small_grid ? w.small_grid : 12288u;
+static bool screen_ok(const Rows& r, const Decider& dc, const MergePlan& p) {
+  return p.small_screen && r.xh && dc.fast && (r.d == 32 || r.d == 64);  // (tiles: d >= 32)
 }
 
 // Iterations below this many positions run every merge class in ONE launch (k_merge_tail) on the
 // main stream: there the cross-stream fork/join (~35 us) costs more than the overlap buys.
 
 template <int D>
-static void launch_groups(const Rows& r, uint32_t* slots, const Decider& dc, const MergeWork& w,
-                          Counters* ctr, uint32_t n, hipStream_t s) {
-  if (n < tail_merge_max(w)) {
+static void launch_groups(const Rows& r, uint32_t* slots, const Decider& dc, const MergePlan& p,
+                          const MergeCall& c, Counters* ctr, uint32_t n, hipStream_t s) {
+  if (n < tail_merge_max(p)) {
     using L896 = BigLayout<D, 896, false>;
     using L384 = BigLayout<D, 384, true>;
     using L192 = BigLayout<D, 192, true>;
@@ -226,52 +230,50 @@ static void launch_groups(const Rows& r, uint32_t* slots, const Decider& dc, con
     (void)lds_ok;
     // options "tail_big_groups" / "tail_small_groups": 32 / 64 / 128 / 256 and 128 / 256 / 512 /
     // 1024 swept (round 3)
-    const uint32_t nbig = w.tail_nbig ? w.tail_nbig : 128u;
-    const uint32_t nsmall = w.tail_nsmall ? w.tail_nsmall : 512u;
-    MergeWork wt = w;
-    wt.big_screen = 0u;
-    if (w.tail_big_screen && screen_ok(r, dc, w)) {
-      screen_margins(r.d, &wt.bs_m0, &wt.bs_a2);
-      wt.bs_s_star = dc.s_star;
-      wt.big_screen = 1u;
-    }
-    if (w.tail_screen && screen_ok(r, dc, w)) {
+    const uint32_t nbig = p.tail_nbig ? p.tail_nbig : 128u;
+    const uint32_t nsmall = p.tail_nsmall ? p.tail_nsmall : 512u;
+    float m0 = 0.0f, a2 = 0.0f;
+    const bool can_screen = screen_ok(r, dc, p);
+    const bool big_screen = p.tail_big_screen && can_screen;
+    const bool small_screen = p.tail_screen && can_screen;
+    if (big_screen || small_screen) screen_margins(r.d, &m0, &a2);
+    if (small_screen) {
       // the fp16 screen of the small runs first (few of them merge this late in the loop), on
       // the same stream: k_merge_tail's small-run waves then take only the runs it passed
-      float m0, a2;
-      screen_margins(r.d, &m0, &a2);
       // (option tail_screen_grid; one box, interleaved C2: 512 → 214.9, 1024 → 210.0, 2048 →
       // 208.1 ms per step; tail_screen = 0: 213.3 ms)
-      const uint32_t sgrid = w.tail_screen_grid ? w.tail_screen_grid : 2048u;
-      k_small_screen<D><<<sgrid, 64, 0, s>>>(w, slots, r, dc.s_star, m0, a2, w.kt);
-      wt.screened = 1u;
+      const uint32_t sgrid = p.tail_screen_grid ? p.tail_screen_grid : 2048u;
+      k_small_screen<D><<<sgrid, 64, 0, s>>>(view(p, c), slots, r, dc.s_star, m0, a2, c.kt);
     }
-    k_merge_tail<D><<<nbig + nsmall, 256, lds, s>>>(wt, slots, dc, r, ctr, nbig);
+    const BigScreen bs = big_screen ? BigScreen{1u, dc.s_star, m0, a2}
+                                    : BigScreen{0u, 0.0f, 0.0f, 0.0f};
+    k_merge_tail<D><<<nbig + nsmall, 256, lds, s>>>(view(p, c, small_screen ? 1u : 0u, bs), slots,
+                                                    dc, r, ctr, nbig);
     return;
   }
-  const Fork f(w, s);
+  const Fork f(p, s);
   // The small-run chain (screen + merge: the merge phase's critical path in 146 of C2's 218
   // multi-launch iterations, rocprofv3 trace) on the main stream: it starts without the fork's
   // cross-stream wait, and at the join only the aux streams are waited for; the >384-row classes
   // on aux 2 (C2, one box, interleaved: 203.9 -> 200.8 ms per step).  Not when the previous
-  // iteration had many 385..896-row runs (w.big896_aux, C4): the long walks are the critical
+  // iteration had many 385..896-row runs (p.big896_aux, C4): the long walks are the critical
   // path there and keep the main stream (C4 989 -> 1120 ms with the small chain on it).
-  const bool long_heavy = w.big896_aux != 0u;
+  const bool long_heavy = p.big896_aux != 0u;
   const hipStream_t s_small = long_heavy ? f.lane(2) : s, s_long = long_heavy ? s : f.lane(2);
   // longest walks first on each stream; the longest runs (few, long walks) on the main stream,
   // concurrent with the auxiliary ones (it waits for them at the join)
-  launch_big<D, 384, 256, true>(w, 2, slots, dc, r, ctr, n, f.lane(0));
-  // many 385..896-row runs (w.big896_aux): they go on aux 2, ahead of the small runs, instead of
+  launch_big<D, 384, 256, true>(p, c, 2, slots, dc, r, ctr, n, f.lane(0));
+  // many 385..896-row runs (p.big896_aux): they go on aux 2, ahead of the small runs, instead of
   // in front of the >896-row runs on the main stream — serialised, the two long-walk classes
   // make the main stream the critical path (C4 1794 -> 1432 ms); with a handful of them (C2)
   // the main stream is the better place (measured 281-285 vs 284-294 ms)
-  if (!long896(w, dc, r))
-    launch_big<D, 896, 256, false>(w, 3, slots, dc, r, ctr, n, w.big896_aux ? f.lane(2) : s_long);
-  launch_huge(w, slots, dc, r, ctr, n, s_long);
+  if (!long896(p, dc, r))
+    launch_big<D, 896, 256, false>(p, c, 3, slots, dc, r, ctr, n, long_heavy ? f.lane(2) : s_long);
+  launch_huge(p, c, slots, dc, r, ctr, n, s_long);
   // 129..192 rows: two workgroups per CU (62 KB of LDS at d = 64, VGPRs capped at 256 like the
   // 65..128 class), ahead of 65..128 on aux 1
-  launch_big<D, 192, 256, true>(w, 1, slots, dc, r, ctr, n, f.lane(1));
-  launch_big<D, 128, 128, true>(w, 0, slots, dc, r, ctr, n, f.lane(1));
+  launch_big<D, 192, 256, true>(p, c, 1, slots, dc, r, ctr, n, f.lane(1));
+  launch_big<D, 128, 128, true>(p, c, 0, slots, dc, r, ctr, n, f.lane(1));
   // every small-run class in one persistent launch (the kernel strides over its batches)
   // HIP events on its own stream too (bench.py's headline cross-check: this launch is alone on
   // aux 2, so the event pair measures it, unlike the big-run classes that wait for CU resources)
@@ -282,32 +284,30 @@ static void launch_groups(const Rows& r, uint32_t* slots, const Decider& dc, con
   // 253.9; small-run merge 79.4 -> 70.5 ms per step)
   // the fp16 screen first (option small_screen, where the row image exists): the merge then
   // takes only the runs it could not rule out
-  if (screen_ok(r, dc, w)) {
+  const bool screened = screen_ok(r, dc, p);
+  if (screened) {
     float m0, a2;
     screen_margins(r.d, &m0, &a2);
     // (option small_screen_grid; one-wave workgroups: 2048 → 207.9 / 207.8 vs 3072 → 211.2 /
     // 211.1 ms per C2 step on one box, 1024 → 227–228, 1536 / 2560 within noise of 2048)
-    const uint32_t sgrid = w.screen_grid ? w.screen_grid : 2048u;
-    k_small_screen<D><<<sgrid, 64, 0, s_small>>>(w, slots, r, dc.s_star, m0, a2, w.kt);
-    MergeWork ws = w;
-    ws.screened = 1u;
-    if (w.small_ev[0]) (void)hipEventRecord(w.small_ev[0], s_small);
-    k_merge_small<D><<<small_grid(w), 64, 0, s_small>>>(ws, slots, dc, r, ctr);
-  } else {
-    if (w.small_ev[0]) (void)hipEventRecord(w.small_ev[0], s_small);
-    k_merge_small<D><<<small_grid(w), 64, 0, s_small>>>(w, slots, dc, r, ctr);
+    const uint32_t sgrid = p.screen_grid ? p.screen_grid : 2048u;
+    k_small_screen<D><<<sgrid, 64, 0, s_small>>>(view(p, c), slots, r, dc.s_star, m0, a2, c.kt);
   }
-  if (w.small_ev[0]) (void)hipEventRecord(w.small_ev[1], s_small);
+  if (c.small_ev[0]) (void)hipEventRecord(c.small_ev[0], s_small);
+  const uint32_t grid = p.small_grid ? p.small_grid : 12288u;  // option "small_grid"
+  k_merge_small<D><<<grid, 64, 0, s_small>>>(view(p, c, screened ? 1u : 0u), slots, dc, r, ctr);
+  if (c.small_ev[0]) (void)hipEventRecord(c.small_ev[1], s_small);
 }
 
 template <int RB, int NT, int KC>
-static void launch_big_wide(const MergeWork& w, int c, uint32_t* slots, const Decider& dc,
-                            const Rows& r, Counters* ctr, uint32_t n, hipStream_t s) {
+static void launch_big_wide(const MergePlan& p, const MergeCall& c, int cls, uint32_t* slots,
+                            const Decider& dc, const Rows& r, Counters* ctr, uint32_t n,
+                            hipStream_t s) {
   using L = BigWideLayout<RB, NT, KC>;
   const auto kern = &k_merge_big_wide<RB, NT, KC>;
   static const bool lds_ok = raise_lds_limit(std::max<size_t>(L::bytes, 96 * 1024), kern);
   (void)lds_ok;
-  launch_big_class(kern, RB, NT, L::bytes, w, c, slots, dc, r, ctr, n, s);
+  launch_big_class(kern, RB, NT, L::bytes, p, c, cls, slots, dc, r, ctr, n, s);
 }
 
 // |G - dot_ref| / (|a||b|) for the bf16x3 Gram value at width d against the reference's sequential
@@ -321,31 +321,32 @@ static float wide_gram_margin(int d) {
 }
 
 static void launch_groups_wide(const Rows& r, uint32_t* slots, const Decider& dc,
-                               const MergeWork& w, Counters* ctr, uint32_t n, hipStream_t s) {
-  auto grid = [&](int c, uint32_t per_wave) {
+                               const MergePlan& p, const MergeCall& c, Counters* ctr, uint32_t n,
+                               hipStream_t s) {
+  auto grid = [&](int cls, uint32_t per_wave) {
     // up to 8192 one-wave workgroups per class (was 2048: C5 2.58 / 2.55 -> 2.36 / 2.33 s per
     // step, interleaved on one box), as for the register-row small-run launch
     // option "wide_group_grid": 4096 -> 1221, 8192 -> 1141, 16384 -> 1103, 32768 -> 1102 ms
     // per C5 step (one box)
-    const uint64_t cap = w.wide_group_grid ? w.wide_group_grid : 16384u;
-    return (uint32_t)std::min<uint64_t>(cap, group_class_capacity(c, n) / per_wave + 1);
+    const uint64_t cap = p.wide_group_grid ? p.wide_group_grid : 16384u;
+    return (uint32_t)std::min<uint64_t>(cap, group_class_capacity(cls, n) / per_wave + 1);
   };
-  const Fork f(w, s);
-  launch_big_wide<384, 256, 32>(w, 2, slots, dc, r, ctr, n, f.lane(0));
-  launch_big_wide<384, 256, 32>(w, 1, slots, dc, r, ctr, n, f.lane(0));  // 129..192 rows
-  launch_big_wide<896, 256, 16>(w, 3, slots, dc, r, ctr, n, f.on ? s : f.lane(0));
-  launch_huge(w, slots, dc, r, ctr, n, f.on ? s : f.lane(0));
-  launch_big_wide<128, 128, 32>(w, 0, slots, dc, r, ctr, n, f.lane(1));
+  const Fork f(p, s);
+  launch_big_wide<384, 256, 32>(p, c, 2, slots, dc, r, ctr, n, f.lane(0));
+  launch_big_wide<384, 256, 32>(p, c, 1, slots, dc, r, ctr, n, f.lane(0));  // 129..192 rows
+  launch_big_wide<896, 256, 16>(p, c, 3, slots, dc, r, ctr, n, f.on ? s : f.lane(0));
+  launch_huge(p, c, slots, dc, r, ctr, n, f.on ? s : f.lane(0));
+  launch_big_wide<128, 128, 32>(p, c, 0, slots, dc, r, ctr, n, f.lane(1));
   // the small-run classes (runs of 2..64 rows), each a persistent launch of up to 16384
   // one-wave workgroups
-  RunCounters* rc = w.rc;
+  RunCounters* rc = p.lists.rc;
   const hipStream_t sl = f.lane(2);
   // (an fp16-image screen of these runs, k_small_screen_wide, ruled out 96 % of C5's small-run
   // rows and still cost more than it saved — 2.25 -> 2.78 s per step — and was removed in round 5)
   // runs of 8..64 rows at d = 512 (C5): pairwise decisions on the matrix cores (option
   // wide_gram) with the margin of the bf16x3 Gram value at this width (wide_gram_margin)
-  const bool gram = w.wide_gram && dc.fast && r.d == 512;
-  const uint32_t gmin = w.wide_gram;  // the smallest group width that decides on the matrix cores
+  const bool gram = p.wide_gram && dc.fast && r.d == 512;
+  const uint32_t gmin = p.wide_gram;  // the smallest group width that decides on the matrix cores
   Decider dg = dc;
   if (gram) {
     const float m = wide_gram_margin(r.d);
@@ -360,9 +361,9 @@ static void launch_groups_wide(const Rows& r, uint32_t* slots, const Decider& dc
   // this 1733 / 1736 (1691 / 1716 on a second box, where two other assignments measured
   // 1679–1713 ms).  Index: 5 - class (64, 32, 16, 8, 4, 2).
   const hipStream_t gs[6] = {s, f.lane(0), sl, f.lane(1), f.lane(1), sl};
-  auto group = [&](auto kern, int c, uint32_t per_wave, const Decider& dd) {
-    kern<<<grid(c, per_wave), 64, 0, gs[5 - c]>>>(w.cls[c], &rc->n_cls[c].v, slots, dd, r, ctr,
-                                                   w.dlist, w.kt);
+  auto group = [&](auto kern, int cls, uint32_t per_wave, const Decider& dd) {
+    kern<<<grid(cls, per_wave), 64, 0, gs[5 - cls]>>>(p.lists.cls[cls], &rc->n_cls[cls].v, slots,
+                                                       dd, r, ctr, c.sink.dlist, c.kt);
   };
   if (gram && gmin <= 64) group(k_merge_group_wide<64, 512>, 5, 1, dg);
   else group(k_merge_group_wide<64>, 5, 1, dc);
@@ -376,53 +377,54 @@ static void launch_groups_wide(const Rows& r, uint32_t* slots, const Decider& dc
   group(k_merge_group_wide<2>, 0, 32, dc);
 }
 
-void launch_runs(const uint32_t* key, uint32_t lo, uint32_t n, int bucket_thr, const MergeWork& w,
-                 hipStream_t s, const uint32_t* n_dev) {
+void launch_runs(const uint32_t* key, uint32_t lo, uint32_t n, int bucket_thr, const MergePlan& p,
+                 const MergeCall& c, hipStream_t s, const uint32_t* n_dev) {
   const uint32_t ntiles = (n + kRunTile - 1) / kRunTile;
   // run_ws: counts [kRunRows][ntiles], tail ends [ntiles], then 8-byte aligned: first / last
   // heads (uint2) [ntiles], head bitmaps [ntiles][64]
-  uint32_t* counts = w.run_ws;
+  uint32_t* counts = p.run_ws;
   uint32_t* tail_ends = counts + (size_t)kRunRows * ntiles;
   uint2* heads_fl = reinterpret_cast<uint2*>(counts + (((kRunRows + 1u) * ntiles + 1u) & ~1u));
   uint64_t* hbits = reinterpret_cast<uint64_t*>(heads_fl + ntiles);
   k_runs_count<<<ntiles, 256, 0, s>>>(key, lo, n, bucket_thr, ntiles, hbits, heads_fl, counts,
-                                      w.kt, n_dev);
+                                      c.kt, n_dev);
   const bool fused = ntiles <= 256u;  // the write kernel scans the counts itself
   if (fused) {
     k_runs_write<true><<<ntiles, 256, 0, s>>>(lo, n, bucket_thr, ntiles, hbits, heads_fl,
-                                              tail_ends, counts, w, n_dev);
+                                              tail_ends, counts, view(p, c), n_dev);
   } else {
-    k_runs_scan<<<kRunRows, 256, 0, s>>>(counts, ntiles, n, bucket_thr, heads_fl, tail_ends, w.rc);
+    k_runs_scan<<<kRunRows, 256, 0, s>>>(counts, ntiles, n, bucket_thr, heads_fl, tail_ends,
+                                            p.lists.rc);
     k_runs_write<false><<<ntiles, 256, 0, s>>>(lo, n, bucket_thr, ntiles, hbits, heads_fl,
-                                               tail_ends, counts, w, nullptr);
+                                               tail_ends, counts, view(p, c), nullptr);
   }
 }
 
 void launch_tail_local(const uint32_t* kin, const uint32_t* vin, uint32_t* kout, uint32_t* vout,
-                       const uint32_t* dtot, int bits, int bucket_thr, const MergeWork& w,
-                       hipStream_t s) {
+                       const uint32_t* dtot, int bits, int bucket_thr, const MergePlan& p,
+                       const MergeCall& c, hipStream_t s) {
   k_tail_local<<<1u << kTailTopBits, 256, 0, s>>>(kin, vin, kout, vout, dtot, bits - kTailTopBits,
-                                                   bucket_thr, w);
+                                                   bucket_thr, view(p, c));
 }
 
 void launch_merge(const Rows& r, const uint32_t* key, uint32_t* slots, uint32_t lo, uint32_t hi,
-                  float thr, int bucket_thr, const MergeWork& w, Counters* ctr, hipStream_t s,
-                  const uint32_t* n_dev, bool runs_ready) {
+                  float thr, int bucket_thr, const MergePlan& p, const MergeCall& c, Counters* ctr,
+                  hipStream_t s, const uint32_t* n_dev, bool runs_ready) {
   if (hi <= lo) return;
   const uint32_t n = hi - lo;
-  if (n_dev && (lo != 0 || n >= tail_merge_max(w))) return;  // (the caller checks)
+  if (n_dev && (lo != 0 || n >= tail_merge_max(p))) return;  // (the caller checks)
   const Decider dc = make_decider(thr);
-  if (!runs_ready) launch_runs(key, lo, n, bucket_thr, w, s, n_dev);
+  if (!runs_ready) launch_runs(key, lo, n, bucket_thr, p, c, s, n_dev);
   // the merge phase of a multi-launch iteration is stamped as a whole too (KC_MERGE: the wall of
   // its concurrent classes, bench.py's roofline phases)
-  MergeWork wm = w;
-  if (w.kt.blk && (n >= tail_merge_max(w) || !project_device_n_ok(r.d))) wm.kt.phase = KC_MERGE;
+  const bool phase = c.kt.blk && (n >= tail_merge_max(p) || !project_device_n_ok(r.d));
+  const MergeCall cm = phase ? c.with_kt(c.kt.with_phase(KC_MERGE)) : c;
   switch (r.d) {
-    case 8: launch_groups<8>(r, slots, dc, wm, ctr, n, s); break;
-    case 16: launch_groups<16>(r, slots, dc, wm, ctr, n, s); break;
-    case 32: launch_groups<32>(r, slots, dc, wm, ctr, n, s); break;
-    case 64: launch_groups<64>(r, slots, dc, wm, ctr, n, s); break;
-    default: launch_groups_wide(r, slots, dc, wm, ctr, n, s);
+    case 8: launch_groups<8>(r, slots, dc, p, cm, ctr, n, s); break;
+    case 16: launch_groups<16>(r, slots, dc, p, cm, ctr, n, s); break;
+    case 32: launch_groups<32>(r, slots, dc, p, cm, ctr, n, s); break;
+    case 64: launch_groups<64>(r, slots, dc, p, cm, ctr, n, s); break;
+    default: launch_groups_wide(r, slots, dc, p, cm, ctr, n, s);
   }
 }
 

@@ -565,10 +565,6 @@ __device__ __forceinline__ bool big_screen_pass(uint32_t b, const uint32_t* slot
   return *flag != 0u;
 }
 
-struct BigScreen {
-  uint32_t on;
-  float s_star, m0, a2;
-};
 
 // The runs li = first, first + stride, ... (< count) of list `list` (size class cls), one
 // workgroup of NT lanes per run, with smem = BigLayout<D, RB, ROWS_LDS>::bytes of LDS.
@@ -819,19 +815,19 @@ __device__ __forceinline__ void big_runs(const uint2* __restrict__ list, int cls
 // would have been empty.
 template <int D, int RB, int NT, bool ROWS_LDS>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RB <= 192 ? 2 : 1))) void k_merge_big(
-    MergeWork w, int cls, uint32_t* __restrict__ slots, Decider dc, Rows r, Counters* ctr) {
+    MergeView w, int cls, uint32_t* __restrict__ slots, Decider dc, Rows r, Counters* ctr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   kt_begin(w.kt, KC_BIG128 + cls);
   const uint32_t count =
       __hip_atomic_load(&w.rc->n_big[cls].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   big_runs<D, RB, NT, ROWS_LDS>(w.big[cls], cls, count, blockIdx.x, gridDim.x, slots, dc, r, ctr,
-                                w.dlist, smem);
+                                w.sink.dlist, smem);
   if constexpr (RB == kBigRows[kBigClasses - 1]) {
     if (w.huge_fold) {
       __syncthreads();  // (the LDS layouts overlap)
       const uint32_t nh =
           __hip_atomic_load(&w.rc->n_huge.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      huge_runs<D, NT>(w.huge, nh, blockIdx.x, gridDim.x, slots, dc, r, w, ctr, smem);
+      huge_runs<D, NT>(w.huge, nh, blockIdx.x, gridDim.x, slots, dc, r, w.sink, ctr, smem);
     }
   }
   kt_end(w.kt, KC_BIG128 + cls);
@@ -841,7 +837,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RB <= 192 ? 
 // streams, ≈35 us per iteration there): workgroups [0, nbig) take the 65..896-row runs (the
 // longest class first), the others run four small-run waves each.
 template <int D>
-__global__ __launch_bounds__(256) void k_merge_tail(MergeWork w, uint32_t* __restrict__ slots,
+__global__ __launch_bounds__(256) void k_merge_tail(MergeView w, uint32_t* __restrict__ slots,
                                                     Decider dc, Rows r, Counters* ctr,
                                                     uint32_t nbig) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -856,22 +852,22 @@ __global__ __launch_bounds__(256) void k_merge_tail(MergeWork w, uint32_t* __res
     // 385..896, 193..384, 129..192, 65..128
     const uint32_t a4 = nh, a3 = a4 + cnt[3], a2 = a3 + cnt[2], a1 = a2 + cnt[1],
                    total = a1 + cnt[0];
-    const BigScreen bs{w.big_screen, w.bs_s_star, w.bs_m0, w.bs_a2};
+    const BigScreen bs = w.bs;
     for (uint32_t li = blockIdx.x; li < total; li += nbig) {  // block-uniform
       if (li < a4)
-        huge_runs<D, 256>(w.huge, li + 1, li, 1u << 30, slots, dc, r, w, ctr, smem);
+        huge_runs<D, 256>(w.huge, li + 1, li, 1u << 30, slots, dc, r, w.sink, ctr, smem);
       else if (li < a3)
         big_runs<D, 896, 256, false>(w.big[3], 3, li - a4 + 1, li - a4, 1u << 30, slots, dc, r,
-                                     ctr, w.dlist, smem);
+                                     ctr, w.sink.dlist, smem);
       else if (li < a2)
         big_runs<D, 384, 256, true>(w.big[2], 2, li - a3 + 1, li - a3, 1u << 30, slots, dc, r, ctr,
-                                    w.dlist, smem, bs);
+                                    w.sink.dlist, smem, bs);
       else if (li < a1)
         big_runs<D, 192, 256, true>(w.big[1], 1, li - a2 + 1, li - a2, 1u << 30, slots, dc, r, ctr,
-                                    w.dlist, smem, bs);
+                                    w.sink.dlist, smem, bs);
       else
         big_runs<D, 128, 256, true>(w.big[0], 0, li - a1 + 1, li - a1, 1u << 30, slots, dc, r, ctr,
-                                    w.dlist, smem, bs);
+                                    w.sink.dlist, smem, bs);
       __syncthreads();
     }
   } else {

@@ -102,10 +102,10 @@ __device__ __forceinline__ void append_slot(bool pred, uint32_t slot, uint32_t* 
 }
 
 // In-place kernels: record `slot` as rewritten once per iteration.
-__device__ __forceinline__ void mark_dirty(uint32_t slot, const MergeWork& w, Counters* ctr) {
-  if (w.dlist && w.mark[slot] != w.stamp) {
-    w.mark[slot] = w.stamp;
-    w.dlist[atomicAdd(&ctr->n_delta, 1u)] = slot;
+__device__ __forceinline__ void mark_dirty(uint32_t slot, const DeltaSink& k, Counters* ctr) {
+  if (k.dlist && k.mark[slot] != k.stamp) {
+    k.mark[slot] = k.stamp;
+    k.dlist[atomicAdd(&ctr->n_delta, 1u)] = slot;
   }
 }
 

@@ -22,7 +22,7 @@ template <int D, int NT>  // D: d at compile time (unrolled dots), 0 = any d
 __device__ __forceinline__ void huge_runs(const uint2* __restrict__ list, uint32_t count,
                                           uint32_t first, uint32_t stride,
                                           uint32_t* __restrict__ slots, const Decider& dc,
-                                          const Rows& r, const MergeWork& w, Counters* ctr,
+                                          const Rows& r, const DeltaSink& sink, Counters* ctr,
                                           unsigned char* smem) {
   constexpr int NW = NT / 64;
   constexpr int kHugeNT = NT;  // (the body below is written for any NT)
@@ -143,7 +143,7 @@ __device__ __forceinline__ void huge_runs(const uint2* __restrict__ list, uint32
           r.nrm[sj] = nn;
           if (in_lds) lq[found] = __builtin_sqrtf(nn);
           link_members(r, si, sj);
-          mark_dirty(sj, w, ctr);
+          mark_dirty(sj, sink, ctr);
           S[i] = S[size - 1];
           if (in_lds) lq[i] = lq[size - 1];
         }
@@ -200,7 +200,7 @@ __device__ __forceinline__ void huge_runs(const uint2* __restrict__ list, uint32
           r.nrm[sj] = nn;
           if (in_lds) lq[found] = __builtin_sqrtf(nn);
           link_members(r, si, sj);
-          mark_dirty(sj, w, ctr);
+          mark_dirty(sj, sink, ctr);
           S[i] = S[size - 1];
           if (in_lds) lq[i] = lq[size - 1];
         }
@@ -227,11 +227,11 @@ template <int D>
 __global__ __launch_bounds__(kHugeNT) void k_merge_huge(const uint2* __restrict__ list,
                                                        const uint32_t* count_ptr,
                                                        uint32_t* __restrict__ slots, Decider dc,
-                                                       Rows r, MergeWork w, Counters* ctr) {
+                                                       Rows r, MergeView w, Counters* ctr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   kt_begin(w.kt, KC_HUGE);
   const uint32_t count = __hip_atomic_load(count_ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  huge_runs<D, kHugeNT>(list, count, blockIdx.x, gridDim.x, slots, dc, r, w, ctr, smem);
+  huge_runs<D, kHugeNT>(list, count, blockIdx.x, gridDim.x, slots, dc, r, w.sink, ctr, smem);
   kt_end(w.kt, KC_HUGE);
 }
 

@@ -130,7 +130,7 @@ __device__ __noinline__ uint32_t long_mem_decide(const float* xp, const float* c
 template <int D>
 __device__ __forceinline__ void long_run(uint32_t p, uint32_t b, uint64_t* __restrict__ P,
                                          uint32_t* __restrict__ slots, const Decider& dc,
-                                         const Rows& r, const MergeWork& w, Counters* ctr,
+                                         const Rows& r, const DeltaSink& sink, Counters* ctr,
                                          unsigned char* smem) {
   constexpr int NT = kLongNT, NW = NT / 64;
   constexpr int KR = LongRegs<D>::KP;               // positions per lane with the row in registers
@@ -409,7 +409,7 @@ __device__ __forceinline__ void long_run(uint32_t p, uint32_t b, uint64_t* __res
         r.head[s] = hd[y];
       }
     }
-    if (w.dlist) append_slot(rewritten, s, w.dlist, &ctr->n_delta);
+    if (sink.dlist) append_slot(rewritten, s, sink.dlist, &ctr->n_delta);
   }
   __syncthreads();
 #ifdef KLSH_MERGE_PROF
@@ -434,7 +434,7 @@ __global__ __launch_bounds__(kLongNT) void k_merge_long(const uint2* __restrict_
                                                         const uint2* __restrict__ list2,
                                                         const uint32_t* count2_ptr,
                                                         uint32_t* __restrict__ slots, Decider dc,
-                                                        Rows r, MergeWork w, Counters* ctr) {
+                                                        Rows r, MergeView w, Counters* ctr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   kt_begin(w.kt, KC_HUGE);
   const uint32_t count = __hip_atomic_load(count_ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -445,19 +445,19 @@ __global__ __launch_bounds__(kLongNT) void k_merge_long(const uint2* __restrict_
     const uint2* l = li < count ? list : list2;
     const uint32_t k = li < count ? li : li - count;
     const uint2 e = l[k];
-    if (e.y <= kLongRows) long_run<D>(e.x, e.y, P, slots, dc, r, w, ctr, smem);
-    else huge_runs<D, kLongNT>(l, k + 1u, k, 1u << 30, slots, dc, r, w, ctr, smem);
+    if (e.y <= kLongRows) long_run<D>(e.x, e.y, P, slots, dc, r, w.sink, ctr, smem);
+    else huge_runs<D, kLongNT>(l, k + 1u, k, 1u << 30, slots, dc, r, w.sink, ctr, smem);
     __syncthreads();
   }
   kt_end(w.kt, KC_HUGE);
 }
 
 // k_merge_long takes the >896-row runs (and with option long_runs = 4 the 385..896-row ones)
-static bool long_ok_for(const MergeWork& w, const Decider& dc, const Rows& r) {
-  return w.long_P && w.long_groups && w.long_off != 1u && dc.fast && (r.d == 16 || r.d == 32);
+static bool long_ok_for(const MergePlan& p, const Decider& dc, const Rows& r) {
+  return p.lists.long_P && p.long_groups && p.long_off != 1u && dc.fast && (r.d == 16 || r.d == 32);
 }
-static bool long896(const MergeWork& w, const Decider& dc, const Rows& r) {
-  return w.long_off == 4u && long_ok_for(w, dc, r);
+static bool long896(const MergePlan& p, const Decider& dc, const Rows& r) {
+  return p.long_off == 4u && long_ok_for(p, dc, r);
 }
 
 }  // namespace klsh

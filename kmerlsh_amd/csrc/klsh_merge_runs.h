@@ -49,7 +49,7 @@ __device__ __forceinline__ int run_class(uint32_t b, int bucket_thr) {
 // The entries of list l (0 <= l < kRunLists).  With a per-lane l this is a vector load from the
 // kernel-argument block, and a store through it waits for that load: the run-listing kernels read
 // the pointers once into an LDS table (run_list_table) instead of once per entry.
-__device__ __forceinline__ uint2* run_list_ptr(const MergeWork& w, int l) {
+__device__ __forceinline__ uint2* run_list_ptr(const RunLists& w, int l) {
   uint2* p = l == kRunLists - 2 ? w.huge : w.over;
 #pragma unroll
   for (int c = 0; c < kBigClasses; ++c) p = l == kGroupClasses + c ? w.big[c] : p;
@@ -62,7 +62,7 @@ __device__ __forceinline__ uint2* run_list_ptr(const MergeWork& w, int l) {
 // typed as global memory: a generic pointer read back from LDS would make every entry store a
 // flat store, which the LDS waits that follow it also wait for.
 using RunListPtr = __attribute__((address_space(1))) uint64_t*;
-__device__ __forceinline__ void run_list_table(const MergeWork& w, RunListPtr* tab) {
+__device__ __forceinline__ void run_list_table(const RunLists& w, RunListPtr* tab) {
   const uint32_t t = threadIdx.x;
   RunListPtr p = (RunListPtr)(uint64_t*)run_list_ptr(w, (int)min(t, (uint32_t)kRunLists - 1u));
   if (t < (uint32_t)kRunLists) tab[t] = p;
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(256) void k_runs_write(uint32_t lo, uint32_t n, int
                                                     const uint2* __restrict__ heads_fl,
                                                     const uint32_t* __restrict__ tail_ends,
                                                     const uint32_t* __restrict__ counts,
-                                                    MergeWork w, const uint32_t* __restrict__ n_dev) {
+                                                    MergeView w, const uint32_t* __restrict__ n_dev) {
   __shared__ uint64_t hb[kRunTile / 64];
   __shared__ uint32_t lbase[kRunLists], lfill[kRunLists];
   __shared__ uint32_t s_tail_end;
@@ -382,7 +382,7 @@ __global__ __launch_bounds__(256) void k_tail_local(const uint32_t* __restrict__
                                                     uint32_t* __restrict__ kout,
                                                     uint32_t* __restrict__ vout,
                                                     const uint32_t* __restrict__ dtot, int lb,
-                                                    int bucket_thr, MergeWork w) {
+                                                    int bucket_thr, MergeView w) {
   // (4 or 8 keys per lane per round measured the same as 16; J adaptive vs always 16: C2 run
   // listing 18.2 vs 18.4 ms per step, one box, three rounds)
   constexpr uint32_t kItems = 16;  // keys per lane per round at most

@@ -450,7 +450,7 @@ __device__ __forceinline__ void pair_batch(const uint2* __restrict__ list, uint3
 // One wave's share of the small-run batches: waves `wave`, `wave + nwaves`, ... of the batch
 // space; lds = this wave's 64 * (D + 4) floats.
 template <int D>
-__device__ __forceinline__ void small_loop(const MergeWork& w, uint32_t* __restrict__ slots,
+__device__ __forceinline__ void small_loop(const MergeView& w, uint32_t* __restrict__ slots,
                                            const Decider& dc, const Rows& r, Counters* ctr,
                                            float* lds, uint32_t wave, uint32_t nwaves) {
   constexpr int NC = kGroupClasses;
@@ -514,12 +514,12 @@ __device__ __forceinline__ void small_loop(const MergeWork& w, uint32_t* __restr
     uint32_t bi;
     locate(t, c, bi);
     switch (c) {  // wave-uniform
-      case 0: pair_batch<D>(lists[0], n[0], bi, slots, dc, r, ctr, w.dlist); break;
-      case 1: merge_batch<4, D>(e.x, e.y, slot, slots, dc, r, lds, w.dlist, ctr); break;
-      case 2: merge_batch<8, D>(e.x, e.y, slot, slots, dc, r, lds, w.dlist, ctr); break;
-      case 3: merge_batch<16, D>(e.x, e.y, slot, slots, dc, r, lds, w.dlist, ctr); break;
-      case 4: merge_batch<32, D>(e.x, e.y, slot, slots, dc, r, lds, w.dlist, ctr); break;
-      default: merge_batch<64, D>(e.x, e.y, slot, slots, dc, r, lds, w.dlist, ctr); break;
+      case 0: pair_batch<D>(lists[0], n[0], bi, slots, dc, r, ctr, w.sink.dlist); break;
+      case 1: merge_batch<4, D>(e.x, e.y, slot, slots, dc, r, lds, w.sink.dlist, ctr); break;
+      case 2: merge_batch<8, D>(e.x, e.y, slot, slots, dc, r, lds, w.sink.dlist, ctr); break;
+      case 3: merge_batch<16, D>(e.x, e.y, slot, slots, dc, r, lds, w.sink.dlist, ctr); break;
+      case 4: merge_batch<32, D>(e.x, e.y, slot, slots, dc, r, lds, w.sink.dlist, ctr); break;
+      default: merge_batch<64, D>(e.x, e.y, slot, slots, dc, r, lds, w.sink.dlist, ctr); break;
     }
     e = e_next;
     slot = slot_next;
@@ -535,7 +535,7 @@ __device__ __forceinline__ void small_loop(const MergeWork& w, uint32_t* __restr
 // 2^-25 absolute per element for subnormals), the screen's f32 sums, the reference's own sequential
 // sums and the quotient's roundings, 1.5x headroom (screen_margins).  A run none of whose pairs
 // reaches s* - m cannot merge: it is left as it is — the walk's result for it is "no change" — and
-// only the others go on to k_merge_small (lists MergeWork::act), which decides them exactly on the
+// only the others go on to k_merge_small (lists RunLists::act), which decides them exactly on the
 // f32 rows.  A row whose image has no usable norm (zero, tiny, fp16 overflow, NaN) keeps its run.
 //
 // The screen is a gather of 64 fp16 rows per batch followed by little arithmetic (the Gram blocks
@@ -549,7 +549,7 @@ __device__ __forceinline__ void small_loop(const MergeWork& w, uint32_t* __restr
 constexpr int kScreenAhead = 2;  // batches whose rows are in flight while one is screened
 
 template <int D>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_small_screen(MergeWork w, const uint32_t* __restrict__ slots,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_small_screen(MergeView w, const uint32_t* __restrict__ slots,
                                                      Rows r, float s_star, float m0, float a2,
                                                      KTime kt) {
   constexpr int NC = kGroupClasses, STH = D + 8;  // LDS row stride in halves (16-B pad)
@@ -706,7 +706,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 
 template <int D>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_merge_small(
-    MergeWork w, uint32_t* __restrict__ slots,
+    MergeView w, uint32_t* __restrict__ slots,
                                                     Decider dc, Rows r, Counters* ctr) {
   __shared__ __attribute__((aligned(16))) float lds[64 * (D + 4)];
   kt_begin(w.kt, KC_SMALL);

@@ -285,12 +285,12 @@ struct BigWideLayout {
 };
 
 template <int RB, int NT, int KC>
-__global__ __launch_bounds__(NT) void k_merge_big_wide(MergeWork w, int cls,
+__global__ __launch_bounds__(NT) void k_merge_big_wide(MergeView w, int cls,
                                                        uint32_t* __restrict__ slots, Decider dc,
                                                        Rows r, Counters* ctr) {
   using L = BigWideLayout<RB, NT, KC>;
   const uint2* __restrict__ list = w.big[cls];
-  uint32_t* const dlist = w.dlist;
+  uint32_t* const dlist = w.sink.dlist;
   RunCounters* const rc = w.rc;
   const KTime kt = w.kt;
   kt_begin(kt, KC_BIG128 + cls);
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(NT) void k_merge_big_wide(MergeWork w, int cls,
     if (w.huge_fold) {  // the >896-row runs too (see k_merge_big)
       const uint32_t nh =
           __hip_atomic_load(&w.rc->n_huge.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      huge_runs<0, NT>(w.huge, nh, blockIdx.x, gridDim.x, slots, dc, r, w, ctr, smem);
+      huge_runs<0, NT>(w.huge, nh, blockIdx.x, gridDim.x, slots, dc, r, w.sink, ctr, smem);
     }
   }
   kt_end(kt, KC_BIG128 + cls);

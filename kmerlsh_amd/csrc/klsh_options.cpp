@@ -46,7 +46,7 @@ const Option kOptions[] = {
     FLAG("phase_timing", phase_timing),
     FLAG("kernel_timing", kernel_timing),
     FLAG("tail_batch", tail_batch),
-    FLAG("huge_fold", huge_fold_always),
+    FLAG("huge_fold", mp.huge_fold_always),
     FLAG("tail_local", tail_local),
     BOOL01("result_device", result_device),
     BOOL01("hyperplane_async", hyperplane_async),
@@ -59,23 +59,23 @@ const Option kOptions[] = {
         if (v < 0 || v > INT32_MAX) return out_of_range("stop_after", "in [0, 2^31)");
         c->stop_after = (int)v;
         return 0;)},
-    {"projection", GET(c->pw.variant), SET(
+    {"projection", GET(c->pp.variant), SET(
         if (v != klsh::kProjAuto && v != klsh::kProjPacked)
           return out_of_range("projection", "0 (default) or 1 (exact packed chains)");
         KLSH_HIP(hipSetDevice(c->device));
-        c->pw.variant = (uint32_t)v;
+        c->pp.variant = (uint32_t)v;
         return c->apply_projection_variant();)},
-    {"wide_gram", GET(c->mw.wide_gram), SET(
+    {"wide_gram", GET(c->mp.wide_gram), SET(
         if (v != 0 && v != 8 && v != 16 && v != 32 && v != 64)
           return out_of_range("wide_gram", "0, 8, 16, 32 or 64");
-        c->mw.wide_gram = (uint32_t)v;
+        c->mp.wide_gram = (uint32_t)v;
         return 0;)},
-    INVERTED01("wide_unrolled", pw.wide_rolled),
-    INVERTED01("h16_bound", pw.h16_cs),
-    // MergeWork::long_off: 0 = on (option value 1), 1 = off (0), 4 = 4
-    {"long_runs", GET(c->mw.long_off == 1u ? 0 : c->mw.long_off == 0u ? 1 : c->mw.long_off), SET(
+    INVERTED01("wide_unrolled", pp.wide_rolled),
+    INVERTED01("h16_bound", pp.v.h16_cs),
+    // MergePlan::long_off: 0 = on (option value 1), 1 = off (0), 4 = 4
+    {"long_runs", GET(c->mp.long_off == 1u ? 0 : c->mp.long_off == 0u ? 1 : c->mp.long_off), SET(
         if (v != 0 && v != 1 && v != 4) return out_of_range("long_runs", "0, 1 or 4");
-        c->mw.long_off = v == 1 ? 0u : v == 0 ? 1u : 4u;
+        c->mp.long_off = v == 1 ? 0u : v == 0 ? 1u : 4u;
         KLSH_HIP(hipSetDevice(c->device));
         return c->cap_slots ? c->ensure_long(c->cap_slots, c->d) : 0;)},
     {"comm_timeout_s", GET(c->comm_timeout_s), SET(
@@ -118,33 +118,34 @@ const Option kOptions[] = {
     COUNT("kcount_db_chunk_records", kcount.db_chunk_records),
     READONLY("kcount_db_chunks", c->kcount.db_chunks),
     READONLY("kcount_db_prefix_used", c->kcount.db_prefix_used),
-    GRID("h16_grid", pw.h16_grid),
-    GRID("h16_segcap", pw.segcap),
-    GRID("wide_grid", pw.wide_grid),
-    GRID("fix_grid", pw.fix_grid),
-    GRID("small_grid", mw.small_grid),
-    GRID("tail_big_groups", mw.tail_nbig),
-    GRID("tail_small_groups", mw.tail_nsmall),
-    GRID("wide_group_grid", mw.wide_group_grid),
-    GRID("small_screen_grid", mw.screen_grid),
-    // one option, kept where each mode's launches read it
-    {"grid_cap", GET(c->mw.grid_cap), SET(
+    GRID("h16_grid", pp.h16_grid),
+    GRID("h16_segcap", pp.segcap),
+    GRID("wide_grid", pp.wide_grid),
+    GRID("fix_grid", pp.fix_grid),
+    GRID("small_grid", mp.small_grid),
+    GRID("tail_big_groups", mp.tail_nbig),
+    GRID("tail_small_groups", mp.tail_nsmall),
+    GRID("wide_group_grid", mp.wide_group_grid),
+    GRID("small_screen_grid", mp.screen_grid),
+    // (modes B and K keep a copy: their sources and sample tables are built over KmcHooks /
+    // KcountHooks alone, without the context)
+    {"grid_cap", GET(c->grid_cap), SET(
         if (int e = grid("grid_cap", v)) return e;
-        c->mw.grid_cap = c->kmc.grid_cap = c->kcount.grid_cap = (uint32_t)v;
+        c->grid_cap = c->kmc.grid_cap = c->kcount.grid_cap = (uint32_t)v;
         return 0;)},
     // capped at the largest size the one-launch merge's parity is pinned at (2^22: C2's
     // iterations of 2^21..2^22 positions, test_mid_local_sort's 2.6M rows); above it, runs over
     // 896 rows at d = 16 / 32 would walk in huge_runs instead of k_merge_long, which no test
     // covers.  Reads back resolved (0 = the default).
-    {"tail_merge_rows", GET(klsh::tail_merge_max(c->mw)), SET(
+    {"tail_merge_rows", GET(klsh::tail_merge_max(c->mp)), SET(
         if (v < 0 || v > (1 << 22)) return out_of_range("tail_merge_rows", "in [0, 2^22]");
-        c->mw.tail_max = (uint32_t)v;
+        c->mp.tail_max = (uint32_t)v;
         return 0;)},
-    CHECKED("small_screen", zero_or_one, mw.small_screen, (uint32_t)v),
+    CHECKED("small_screen", zero_or_one, mp.small_screen, (uint32_t)v),
     BOOL01("hip_events", hip_events),
-    CHECKED("tail_screen", zero_or_one, mw.tail_screen, (uint32_t)v),
-    GRID("tail_screen_grid", mw.tail_screen_grid),
-    CHECKED("tail_big_screen", zero_or_one, mw.tail_big_screen, (uint32_t)v),
+    CHECKED("tail_screen", zero_or_one, mp.tail_screen, (uint32_t)v),
+    GRID("tail_screen_grid", mp.tail_screen_grid),
+    CHECKED("tail_big_screen", zero_or_one, mp.tail_big_screen, (uint32_t)v),
     READONLY("result_rounds", c->result_rounds),
     READONLY("result_rank_us", c->result_rank_us),
     READONLY("member_nodes", c->loaded ? c->members : 0),

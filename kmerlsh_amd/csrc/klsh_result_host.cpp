@@ -17,7 +17,7 @@ static int device_result(klsh_ctx* ctx, uint32_t* d_off, uint32_t* d_nodes, uint
                          uint64_t* total_out) {
   const uint64_t n = ctx->n_live, M = ctx->members;
   const bool rank = (d_nodes || d_labels) && M;
-  const uint32_t cap = ctx->mw.grid_cap;
+  const uint32_t cap = ctx->grid_cap;
   hipStream_t s = ctx->stream;
   klsh::DevBuf<uint32_t> hdr, tsum, off_tmp, rowof;
   klsh::DevBuf<uint64_t> st0, st1;

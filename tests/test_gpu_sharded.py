@@ -274,7 +274,7 @@ def test_sharded_failure_aborts_the_group():
 # ---------------------------------------------------------------------------------------------
 # Every merge class's delta listing and the replicas' state.  A sharded merge has two things to
 # get right: the merge itself, and listing each slot it rewrote (append_slot / mark_dirty into
-# MergeWork::dlist, written separately in each kernel) — the only way the other ranks' replicas
+# DeltaSink::dlist, written separately in each kernel) — the only way the other ranks' replicas
 # learn of it, through k_delta_apply, which is also the only writer of a replica's nrm, cnt, tail
 # and fp16 image.  The cases below send runs of every class through the per-class launches (and
 # k_merge_tail) at every width, sharded, and read every rank's cached state back.
