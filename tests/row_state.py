@@ -12,7 +12,8 @@ offsets say it must be.  No tolerances: a cache that is off by one ulp is a wron
 Also here: the seeded inputs of the state tests ("spread" single-bucket rows, "ladder" loop rows),
 the projection tests' adversarial rows, the result comparison and the options context manager,
 shared by test_gpu_parity.py, test_gpu_row_state.py, test_gpu_sharded.py,
-test_gpu_launch_geometry.py and test_gpu_widths.py.
+test_gpu_launch_geometry.py, test_gpu_widths.py and test_gpu_small_loops.py, and `clustered`,
+the seeded group rows of the parity, sharded, width and small-loop tests (the one definition).
 """
 import numpy as np
 
@@ -136,6 +137,13 @@ def weights(rng, n, hi):
     off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint64)
     ids = rng.permutation(int(off[-1])).astype(np.uint64)
     return off, ids
+
+
+def clustered(rng, n, d, groups, noise):
+    """n rows around `groups` normal centers, each a center plus normal noise of that sigma."""
+    centers = rng.normal(0, 1, size=(groups, d)).astype(np.float32)
+    return (centers[rng.integers(0, groups, n)] +
+            rng.normal(0, noise, size=(n, d)).astype(np.float32)).astype(np.float32)
 
 
 def spread(b, d):

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, GOLDEN)
 import make_golden_thr  # noqa: E402
 from make_golden_thr import threshold_rows  # noqa: E402
-from row_state import (adversarial_rows, assert_same_result, options,  # noqa: E402
+from row_state import (adversarial_rows, assert_same_result, clustered, options,  # noqa: E402
                        same_bits)
 
 
@@ -51,18 +51,46 @@ def test_hash_keys_match_reference(engine, name):
     (100_000, 17, 1 << 17), (300_000, 23, 1000), (1_000_003, 22, 1 << 22), (5_000_000, 23, 1 << 23),
     (200_000, 31, 1 << 31), (70_000, 0, 1),
     (390_000, 18, 1 << 18), (1_500_000, 20, 1 << 20), (300_000, 19, 700), (150_000, 17, 1 << 17),
+    # either side of one, two and eight 4096-key tiles (kSortTile; 2047..2049 above are inside one)
+    (4095, 12, 1 << 12), (4096, 12, 300), (4097, 13, 1 << 13), (8191, 13, 5), (8192, 16, 1 << 16),
+    (8193, 13, 1 << 13), (32769, 15, 1 << 15),
+] + [
+    # every key width over two tiles: P = 1..4 passes of B = 8, 9 or 10 bits (bits 10 | 11, 20 | 21
+    # and 30 | 31 are the pass boundaries; 32: no bit masked off)
+    (5000, bits, 1 << bits) for bits in range(1, 33)
 ])
 def test_bucket_sort_is_stable_counting_sort(engine, n, bits, spread):
     """merge_hashtable (cluster.cc:15-30) scatters rows into lsh_table[key] in row order: the
-    stable bucket order, i.e. numpy's stable argsort of the keys (single-pass look-back sort)."""
+    stable bucket order, i.e. numpy's stable argsort of the keys (LSD passes of 4096-key tiles)."""
     rng = np.random.default_rng(n + bits)
     keys = rng.integers(0, spread, n, dtype=np.uint64).astype(np.uint32)
     if bits < 32:
         keys &= np.uint32((1 << bits) - 1) if bits else np.uint32(0)
+    check_bucket_sort(engine, keys, bits)
+
+
+def check_bucket_sort(engine, keys, bits):
     got_k, got_p = engine.bucket_sort(keys, bits)
     want = np.argsort(keys, kind="stable")
     assert np.array_equal(got_p, want.astype(np.uint32))
     assert np.array_equal(got_k, keys[want])
+
+
+@pytest.mark.parametrize("bits,digit", [(16, 0), (16, 1), (27, 1), (32, 3)])
+def test_bucket_sort_keys_share_one_digit(engine, bits, digit):
+    """Every key holds the same value in one digit of the sort (B = 8, 9, 8 bits wide): that
+    pass's scatter moves each tile as one run to where it was, the other passes still order it."""
+    n = 9000
+    passes = (bits + 9) // 10
+    width = max(8, (bits + passes - 1) // passes)
+    rng = np.random.default_rng(bits * 4 + digit)
+    keys = rng.integers(0, 1 << bits, n, dtype=np.uint64).astype(np.uint32)
+    field = np.uint32(((1 << width) - 1) << (digit * width) & 0xFFFFFFFF)
+    keys = (keys & ~field) | (np.uint32(0x155 << (digit * width) & 0xFFFFFFFF) & field)
+    if bits < 32:
+        keys &= np.uint32((1 << bits) - 1)
+    assert np.unique(keys & field).size == 1 and np.unique(keys).size >= 200  # (16 bits: 256)
+    check_bucket_sort(engine, keys, bits)
 
 
 def test_bucket_sort_repeated_calls(engine):
@@ -806,12 +834,6 @@ def test_convert_matches_reference(engine):
     assert np.array_equal(ids, z["out_ids"])
     assert np.array_equal(np.diff(off), np.ones(len(ids), np.uint64))
     assert same_bits(rows, z["out_rows"])
-
-
-def clustered(rng, n, d, groups, noise):
-    centers = rng.normal(0, 1, size=(groups, d)).astype(np.float32)
-    return (centers[rng.integers(0, groups, n)] +
-            rng.normal(0, noise, size=(n, d)).astype(np.float32)).astype(np.float32)
 
 
 @pytest.mark.parametrize("n,d,groups,iters,bthr", [

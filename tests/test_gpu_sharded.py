@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 from conftest import golden
-from row_state import (LADDER_CALL, LADDER_SHAPES, assert_row_state, check_state, ladder_reference,
-                       options)
+from row_state import (LADDER_CALL, LADDER_SHAPES, assert_row_state, check_state, clustered,
+                       ladder_reference, options)
 
 pytestmark = pytest.mark.gpu
 
@@ -118,12 +118,6 @@ def test_sharded_weighted_matches_reference():
         rows, off, ids = results[r]
         assert np.array_equal(off, z["out_off"]) and np.array_equal(ids, z["out_ids"])
         assert same_bits(rows, z["out_rows"])
-
-
-def clustered(rng, n, d, groups, noise):
-    centers = rng.normal(0, 1, size=(groups, d)).astype(np.float32)
-    return (centers[rng.integers(0, groups, n)] +
-            rng.normal(0, noise, size=(n, d)).astype(np.float32)).astype(np.float32)
 
 
 @pytest.mark.parametrize("world,n,d,groups,iters,bthr", [

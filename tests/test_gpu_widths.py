@@ -26,10 +26,9 @@ import pytest
 import torch  # (before the engine's first use of the device, as test_gpu_result_device.py)
 
 from kmerlsh_amd import _native
-from row_state import (LADDER_CALL, adversarial_rows, assert_same_result, check, ladder_reference,
-                       options, weights)
+from row_state import (LADDER_CALL, adversarial_rows, assert_same_result, check, clustered,
+                       ladder_reference, options, weights)
 from test_gpu_launch_geometry import BIG, NESTED, class_counts, ids_of
-from test_gpu_sharded import clustered
 
 pytestmark = pytest.mark.gpu
 
