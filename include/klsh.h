@@ -134,6 +134,38 @@ int klsh_load_rows(klsh_ctx* ctx, const float* rows, uint64_t n, int d,
 int klsh_load_rows_device(klsh_ctx* ctx, const float* d_rows, uint64_t n, int d,
                           uint64_t row_stride, const uint64_t* member_ids);
 
+/* Rows that already have member lists, from device memory: the inverse of klsh_result_device,
+ * and what klsh_load_rows(rows, n, d, member_offsets, member_ids) does for host arrays.  d_rows,
+ * n, d and row_stride as in klsh_load_rows_device.  d_member_offsets (device, n + 1 entries) and
+ * d_member_nodes (device, or NULL) give the lists: row i's members are d_member_nodes[offsets[i]
+ * .. offsets[i + 1]), absolute indices — offsets[0] need not be 0, so a window `offsets + a` of a
+ * longer array loads rows a.. of a concatenated set against its whole node array; m = offsets[n]
+ * - offsets[0].  d_member_nodes NULL: entry q is node q - offsets[0].  The offsets must increase
+ * strictly (a row without members would weigh 0/0 in a consensus).
+ * Nodes are the caller's numbers in [0, M), no node twice; a node in no list is held by no row
+ * (klsh_labels: KLSH_NO_LABEL, like a row klsh_load_counts dropped); option "member_nodes" reads M.
+ *   n_nodes = M > 0  a new node space: member_ids (HOST memory, M entries, or NULL = k) is the id
+ *                    of node k; m <= M
+ *   n_nodes = 0      keep: the node space and the host-side ids of the context's current load stay
+ *                    (member_ids must be NULL; KLSH_E_STATE if nothing is loaded) — the round trip
+ *                    of klsh_result_device's outputs, whole, filtered or sliced, with no id leaving
+ *                    the host vector and no host work per node
+ * Leaves the state klsh_load_rows(rows, n, d, offsets - offsets[0], ids[nodes]) leaves, the nodes
+ * numbered the caller's way: klsh_count, klsh_result and klsh_row_state give the same bytes,
+ * klsh_result_device and klsh_labels speak in the caller's nodes.  The lists are checked and linked
+ * by kernels, per entry (one row may hold every member).  Complete, and the three device arrays no
+ * longer read, when it returns.  n = 0 is an empty load (the offsets may be NULL).
+ * Refused before the context is touched, the previous load intact — KLSH_E_ARG: a host or
+ * foreign-device pointer, row_stride < d, offsets not strictly increasing, m > M, a node >= M, a
+ * node listed twice, member_ids with n_nodes = 0; KLSH_E_RANGE: d outside [1, 4096], n or M >=
+ * 2^32.  klsh_last_error names the check and the smallest offending row or entry. */
+int klsh_load_clusters_device(klsh_ctx* ctx, const float* d_rows, uint64_t n, int d,
+                              uint64_t row_stride,
+                              const uint32_t* d_member_offsets, /* device, n + 1 entries */
+                              const uint32_t* d_member_nodes,   /* device, or NULL */
+                              uint64_t n_nodes,                 /* M, or 0 = keep */
+                              const uint64_t* member_ids);      /* HOST, M entries, or NULL */
+
 /* Mode-C producer on the GPU (reference io/ioHT.cc:59-81 ReadHT + io/ioMatrix.cc:353-408
  * convertHTMat): counts is the whole sample-major kmer_count.bin image (d columns of n_total
  * uint16), the batch is rows [batch_offset, batch_offset+batch_size); v_kmers[j] =
@@ -253,7 +285,8 @@ int klsh_result(klsh_ctx* ctx, float* rows, uint64_t* member_offsets, uint64_t* 
  *   after klsh_load_rows         node k is entry k of the loaded member_ids (row k when
  *                                member_offsets is NULL),
  *   after klsh_load_rows_device  node k is input row k,
- *   after klsh_load_counts       node k is batch row k (the dropped rows included).
+ *   after klsh_load_counts       node k is batch row k (the dropped rows included),
+ *   after klsh_load_clusters_device  node k is the caller's node k (n_nodes = 0: what it was).
  * Ids stay on the host: with `ids` the loaded member ids in node order, klsh_result's
  * member_ids[m] equals ids[nodes[m]].
  * klsh_result_device writes, into memory of the context's device (each may be NULL; a host

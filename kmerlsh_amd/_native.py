@@ -39,6 +39,7 @@ EXPORTED = (
     "klsh_kmc_info", "klsh_khtable_first", "klsh_bucket_runs", "klsh_row_state",
     "klsh_count_khtable", "klsh_kcount_listing", "klsh_count_kmc",
     "klsh_load_rows_device", "klsh_result_device", "klsh_labels",
+    "klsh_load_clusters_device",
 )
 
 
@@ -202,6 +203,8 @@ def load_library() -> ctypes.CDLL:
         "klsh_load_rows": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int, _P, _P]),
         "klsh_load_rows_device": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int,
                                                  ctypes.c_uint64, _P]),
+        "klsh_load_clusters_device": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int,
+                                                     ctypes.c_uint64, _P, _P, ctypes.c_uint64, _P]),
         "klsh_result_device": (ctypes.c_int, [_P, _P, _P, _P, _P]),
         "klsh_labels": (ctypes.c_int, [_P, _P]),
         "klsh_load_counts": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64,
@@ -526,6 +529,56 @@ class Engine:
         torch.cuda.current_stream(rows.device).synchronize()  # the caller's writes are complete
         _check(self._lib.klsh_load_rows_device(self._ctx, ctypes.c_void_p(rows.data_ptr()), n, d,
                                                stride, _ptr(mi)), "klsh_load_rows_device")
+        self.d = d
+
+    def load_clusters(self, rows, member_offsets, member_nodes=None, n_nodes: int | None = None,
+                      member_ids: np.ndarray | None = None) -> None:
+        """Rows with their member lists, all on this engine's GPU (``klsh_load_clusters_device``):
+        rows as in load_rows (float32, 2-D, last-dimension stride 1, row stride >= d),
+        member_offsets (n + 1) and member_nodes (or None: entry q is node q - offsets[0]) 1-D
+        contiguous uint32 or int32 tensors; row i holds nodes[offsets[i]:offsets[i + 1]], so a
+        slice ``off[a:b + 1]`` goes with the whole node tensor.  n_nodes=None keeps the node
+        space and the ids of the current load (the round trip of result_device()); n_nodes=M
+        starts a new one, member_ids (numpy uint64 on the host, M entries, or None = k) its
+        ids."""
+        torch = _torch_if_tensor(rows)
+        if torch is None:
+            raise KlshError("load_clusters: rows must be a torch tensor on the engine's GPU")
+        dev = self._torch_device(torch)
+        if rows.device != dev:
+            raise KlshError(f"load_clusters: the tensor is on {rows.device}, this engine on {dev}")
+        if rows.dtype != torch.float32 or rows.dim() != 2:
+            raise KlshError("load_clusters: the rows must be float32 and 2-D")
+        n, d = rows.shape
+        if (d > 1 and rows.stride(1) != 1) or (n > 1 and rows.stride(0) < d):
+            raise KlshError("load_clusters: the rows need last-dimension stride 1 and a row "
+                            f"stride >= d (strides {tuple(rows.stride())})")
+        stride = rows.stride(0) if n > 1 else d
+        for name, t in (("member_offsets", member_offsets), ("member_nodes", member_nodes)):
+            if t is None and name == "member_nodes":
+                continue
+            if (_torch_if_tensor(t) is None or t.device != dev or t.dim() != 1 or
+                    not t.is_contiguous() or t.dtype not in (torch.uint32, torch.int32)):
+                raise KlshError(f"load_clusters: {name} must be a 1-D contiguous uint32 or int32 "
+                                f"tensor on {dev}")
+        if member_offsets.numel() != n + 1:
+            raise KlshError("load_clusters: member_offsets needs one entry per row and one more")
+        if n_nodes is None and member_ids is not None:
+            raise KlshError("load_clusters: member_ids belong to a new node space (give n_nodes)")
+        if n_nodes is not None and n_nodes <= 0:
+            raise KlshError("load_clusters: n_nodes must be positive (None keeps the loaded nodes)")
+        mi = None if member_ids is None else np.ascontiguousarray(member_ids, np.uint64)
+        if mi is not None and mi.size != n_nodes:
+            raise KlshError("load_clusters: one member id per node")
+
+        def p(t):
+            return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+        torch.cuda.current_stream(dev).synchronize()  # the caller's writes are complete
+        _check(self._lib.klsh_load_clusters_device(self._ctx, p(rows), n, d, stride,
+                                                   p(member_offsets), p(member_nodes),
+                                                   n_nodes or 0, _ptr(mi)),
+               "klsh_load_clusters_device")
         self.d = d
 
     def load_counts(self, counts: np.ndarray, v_kmers: np.ndarray, batch_offset: int = 0,

@@ -614,6 +614,126 @@ int klsh_load_rows_device(klsh_ctx* ctx, const float* d_rows, uint64_t n, int d,
   return 0;
 }
 
+// The checks of klsh_load_clusters_device that need the lists themselves, into scratch of the
+// call alone (nothing of the context is written): offsets strictly increasing, m <= M, every node
+// below M and listed once.  Leaves *m_out = off[n] - off[0], *base_out = off[0] and the start
+// map the link pass reads.
+static int check_clusters(klsh_ctx* ctx, uint64_t n, const uint32_t* d_off, const uint32_t* d_nodes,
+                          uint64_t M, klsh::DevBuf<uint8_t>& start, uint64_t* m_out,
+                          uint32_t* base_out) {
+  hipStream_t s = ctx->stream;
+  const uint32_t cap = ctx->grid_cap;
+  klsh::DevBuf<unsigned long long> err;
+  klsh::DevBuf<uint32_t> owner;
+  if (int e = dalloc(err, 1)) return e;
+  uint32_t ends[2] = {0, 0};
+  KLSH_HIP(hipMemsetAsync(err, 0xFF, sizeof(unsigned long long), s));
+  KLSH_HIP(hipMemcpyAsync(&ends[0], d_off, 4, hipMemcpyDeviceToHost, s));
+  KLSH_HIP(hipMemcpyAsync(&ends[1], d_off + n, 4, hipMemcpyDeviceToHost, s));
+  KLSH_HIP(hipStreamSynchronize(s));
+  // what m is if the offsets increase; if they do not, the row check below refuses the load
+  const uint64_t m = ends[1] > ends[0] ? (uint64_t)ends[1] - ends[0] : 0;
+  const bool fits = m && m <= M;
+  if (fits) {
+    if (int e = dalloc(start, m)) return e;
+    KLSH_HIP(hipMemsetAsync(start, 0, m, s));
+  }
+  unsigned long long bad = 0;
+  auto read_err = [&]() -> int {
+    KLSH_HIP(hipGetLastError());
+    KLSH_HIP(hipMemcpyAsync(&bad, err, sizeof(bad), hipMemcpyDeviceToHost, s));
+    KLSH_HIP(hipStreamSynchronize(s));
+    return 0;
+  };
+  klsh::launch_clusters_check_rows(d_off, (uint32_t)n, (uint32_t)m, fits ? start.get() : nullptr,
+                                   err, s, cap);
+  if (int e = read_err()) return e;
+  if (bad != ~0ull)
+    return fail(KLSH_E_ARG, "d_member_offsets is not strictly increasing at row " +
+                                std::to_string(bad >> 2) + " (a row needs a member)");
+  if (m > M)
+    return fail(KLSH_E_ARG, "the lists hold " + std::to_string(m) + " entries, more than the " +
+                                std::to_string(M) + " nodes");
+  if (d_nodes) {
+    if (int e = dalloc(owner, M)) return e;
+    KLSH_HIP(hipMemsetAsync(owner, 0xFF, sizeof(uint32_t) * M, s));
+    klsh::launch_clusters_check_nodes(d_nodes + ends[0], (uint32_t)m, (uint32_t)M, owner, err, s,
+                                      cap);
+    if (int e = read_err()) return e;
+    if (bad != ~0ull) {
+      const uint64_t q = bad >> 2;  // (an entry of the window; the caller's index adds off[0])
+      uint32_t node = 0, first = 0;
+      KLSH_HIP(hipMemcpy(&node, d_nodes + ends[0] + q, 4, hipMemcpyDeviceToHost));
+      const std::string at = "entry " + std::to_string(ends[0] + q) + " of d_member_nodes";
+      if ((bad & 3) == klsh::kLcErrRange)
+        return fail(KLSH_E_ARG, at + " is node " + std::to_string(node) + ", not below the " +
+                                    std::to_string(M) + " nodes");
+      KLSH_HIP(hipMemcpy(&first, owner + node, 4, hipMemcpyDeviceToHost));
+      return fail(KLSH_E_ARG, at + " lists node " + std::to_string(node) + " twice (first at entry " +
+                                  std::to_string((uint64_t)ends[0] + first) + ")");
+    }
+  }
+  *m_out = m;
+  *base_out = ends[0];
+  return 0;
+}
+
+// Rows with their member lists from device memory: the state klsh_load_rows
+// leaves for the same rows and lists, the lists linked by kernels, the nodes the caller's numbers.
+int klsh_load_clusters_device(klsh_ctx* ctx, const float* d_rows, uint64_t n, int d,
+                              uint64_t row_stride, const uint32_t* d_member_offsets,
+                              const uint32_t* d_member_nodes, uint64_t n_nodes,
+                              const uint64_t* member_ids) {
+  if (!ctx || (n && (!d_rows || !d_member_offsets))) return fail(KLSH_E_ARG, "null argument");
+  if (d <= 0 || d > 4096) return fail(KLSH_E_RANGE, "d must be in [1, 4096]");
+  if (row_stride < (uint64_t)d) return fail(KLSH_E_ARG, "row_stride is smaller than d");
+  if (n >= 0xFFFFFFF0ull || n_nodes >= 0xFFFFFFF0ull)
+    return fail(KLSH_E_RANGE, "rows or nodes >= 2^32");
+  const bool keep = n_nodes == 0;  // the node space and the ids of the current load stay
+  if (keep && member_ids)
+    return fail(KLSH_E_ARG, "member_ids given with n_nodes = 0 (the loaded ids are kept)");
+  if (keep && !ctx->loaded) return fail(KLSH_E_STATE, "n_nodes = 0 keeps a load, and nothing is loaded");
+  KLSH_HIP(hipSetDevice(ctx->device));
+  const uint64_t M = keep ? ctx->members : n_nodes;
+  klsh::DevBuf<uint8_t> start;
+  uint64_t m = 0;
+  uint32_t base = 0;
+  if (n) {
+    if (int e = ctx->check_device_ptr(d_rows, "d_rows")) return e;
+    if (int e = ctx->check_device_ptr(d_member_offsets, "d_member_offsets")) return e;
+    if (d_member_nodes)
+      if (int e = ctx->check_device_ptr(d_member_nodes, "d_member_nodes")) return e;
+    if (int e = check_clusters(ctx, n, d_member_offsets, d_member_nodes, M, start, &m, &base))
+      return e;
+  }
+  if (int e = ctx->reserve(n, M, d)) return e;
+  hipStream_t s = ctx->stream;
+  ctx->loaded = false;  // (the state below replaces the previous load's, step by step)
+  if (n) {
+    KLSH_HIP(hipMemsetAsync(ctx->rows.x, 0, sizeof(float) * n * ctx->dp, s));
+    KLSH_HIP(hipMemcpy2DAsync(ctx->rows.x, sizeof(float) * ctx->dp, d_rows,
+                              sizeof(float) * row_stride, sizeof(float) * d, n,
+                              hipMemcpyDeviceToDevice, s));
+  }
+  klsh::launch_clusters_link(ctx->rows, ctx->order, d_member_offsets,
+                             d_member_nodes ? d_member_nodes + base : nullptr, start, (uint32_t)n,
+                             (uint32_t)m, (uint32_t)M, s, ctx->grid_cap);
+  klsh::launch_norms(ctx->rows, (uint32_t)n, s);
+  KLSH_HIP(hipGetLastError());
+  if (!keep) {
+    ctx->ids.resize(M);
+    for (uint64_t k = 0; k < M; ++k) ctx->ids[k] = member_ids ? member_ids[k] : k;
+  }
+  ctx->slots = n;
+  ctx->members = M;
+  klsh::launch_shadow_build(ctx->rows, ctx->slots, s);
+  KLSH_HIP(hipGetLastError());
+  KLSH_HIP(hipStreamSynchronize(s));  // the caller may release its three arrays
+  ctx->n_live = n;
+  ctx->loaded = true;
+  return 0;
+}
+
 int klsh_load_counts(klsh_ctx* ctx, const uint16_t* counts, uint64_t n_total,
                      uint64_t batch_offset, uint64_t batch_size, int d, const float* v_kmers) {
   if (!ctx || !counts || !v_kmers) return fail(KLSH_E_ARG, "null argument");

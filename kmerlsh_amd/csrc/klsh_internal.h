@@ -478,6 +478,25 @@ void launch_result_emit(const uint64_t* st, const uint32_t* rowof, const uint32_
 // cnt = 1, head = tail = order = i, nxt = kNil for i < n (rows loaded as singletons)
 void launch_init_singletons(const Rows& r, uint32_t* order, uint32_t n, hipStream_t s,
                             uint32_t grid_cap = 0);
+// Clustered rows from device memory (klsh_load_clusters_device): off = the caller's n + 1 member
+// offsets, nodes = the caller's node array at entry off[0] (null: entry q is node q), m = off[n] -
+// off[0] entries.  *err (preset to ~0) = the smallest (index << 2 | kLcErr*) a check refused.
+constexpr uint32_t kLcErrOffsets = 0;  // index = a row with off[i + 1] <= off[i]
+constexpr uint32_t kLcErrRange = 1;    // index = an entry whose node is not below `members`
+constexpr uint32_t kLcErrTwice = 2;    // index = an entry whose node an earlier entry lists
+// rows: strictly increasing offsets; start[off[i] - off[0]] = 1 (m bytes, zeroed by the caller;
+// null: check only)
+void launch_clusters_check_rows(const uint32_t* off, uint32_t n, uint32_t m, uint8_t* start,
+                                unsigned long long* err, hipStream_t s, uint32_t grid_cap = 0);
+// entries: every node below `members`, none twice; owner (members words, preset to kNil) ends as
+// the first entry listing each node
+void launch_clusters_check_nodes(const uint32_t* nodes, uint32_t m, uint32_t members,
+                                 uint32_t* owner, unsigned long long* err, hipStream_t s,
+                                 uint32_t grid_cap = 0);
+// checked input -> r.nxt (kNil for every node in no list), r.cnt, r.head, r.tail, order = identity
+void launch_clusters_link(const Rows& r, uint32_t* order, const uint32_t* off,
+                          const uint32_t* nodes, const uint8_t* start, uint32_t n, uint32_t m,
+                          uint32_t members, hipStream_t s, uint32_t grid_cap = 0);
 
 // Floating-point self test: sqrt_out[i] = sqrtf(a[i]); div_out[i] = a[i] / b[i] as the merge
 // kernels evaluate them.

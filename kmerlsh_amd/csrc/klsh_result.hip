@@ -1,6 +1,7 @@
 // gfx950 kernels of the device-side result: member offsets by a three-launch scan,
 // the member lists flattened by list ranking (pointer jumping, a fixed number of rounds), the
-// label of every member node, and the singleton state of a load from device memory.  Integer
+// label of every member node, the singleton state of a load from device memory, and the member
+// state of a load of clustered rows (offsets and nodes back into linked lists).  Integer
 // bookkeeping only.  Every kernel strides over its index range on its own (no workgroup waits for
 // another), so every launch takes option "grid_cap".
 #include <hip/hip_runtime.h>
@@ -279,6 +280,111 @@ void launch_init_singletons(const Rows& r, uint32_t* order, uint32_t n, hipStrea
   if (n)
     k_init_singletons<<<res_grid(n, 256, grid_cap), 256, 0, s>>>(r.cnt, r.head, r.tail, order,
                                                                  r.nxt, n);
+}
+
+// ------------------------------------------------------------------- (f) clustered load --------
+// The list ranking run backwards (klsh_load_clusters_device): n + 1 member offsets and a flat
+// node array in, cnt / head / tail / nxt out.  Entry q is entry off[0] + q of the caller's node
+// array (`nodes` points at it; null: entry q is node q).  The two checking kernels write only the
+// call's scratch; the two linking kernels run after the host has read the error word.
+namespace {
+
+// *err = the smallest (index << 2 | kind) reported: what the host names never depends on which
+// lane got there first
+__device__ __forceinline__ void lc_report(unsigned long long* err, uint64_t index, uint32_t kind) {
+  atomicMin(err, (unsigned long long)(index << 2 | kind));
+}
+
+}  // namespace
+
+// Over rows: off[i] < off[i + 1], and start[off[i] - off[0]] = 1 (start: m bytes, zeroed, or null
+// when the end points alone rule the load out; an offset outside [off[0], off[0] + m) marks
+// nothing, and the row before or after it is reported).
+__global__ __launch_bounds__(256) void k_lc_check_rows(const uint32_t* __restrict__ off, uint32_t n,
+                                                       uint32_t m, uint8_t* __restrict__ start,
+                                                       unsigned long long* __restrict__ err) {
+  const uint32_t base = off[0];
+  const uint64_t stride = (uint64_t)gridDim.x * 256u;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += stride) {
+    const uint32_t a = off[i], b = off[i + 1];
+    if (b <= a)
+      lc_report(err, i, kLcErrOffsets);
+    else if (start && a >= base && a - base < m)
+      start[a - base] = 1;
+  }
+}
+
+// Over entries: node < members, and no node twice.  owner[v] (preset to kNil) ends as the first
+// entry that lists v.  Of the entries listing one node, every atomicMin but the first to arrive
+// sees an earlier arrival, and the larger of the two is a repeat; whatever the order, the second
+// smallest entry is reported (when it arrives after the smallest, or the smallest after it) and
+// the smallest never is.
+__global__ __launch_bounds__(256) void k_lc_check_nodes(const uint32_t* __restrict__ nodes,
+                                                        uint32_t m, uint32_t members,
+                                                        uint32_t* __restrict__ owner,
+                                                        unsigned long long* __restrict__ err) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256u;
+  for (uint64_t q = (uint64_t)blockIdx.x * 256u + threadIdx.x; q < m; q += stride) {
+    const uint32_t v = nodes[q];
+    if (v >= members) {
+      lc_report(err, q, kLcErrRange);
+      continue;
+    }
+    const uint32_t seen = atomicMin(&owner[v], (uint32_t)q);
+    if (seen != kNil) lc_report(err, max(seen, (uint32_t)q), kLcErrTwice);
+  }
+}
+
+// Over entries: the node of entry q links to the node of entry q + 1 unless that entry starts the
+// next list (nxt preset to kNil, which is what the nodes in no list keep).  No entry needs its row.
+__global__ __launch_bounds__(256) void k_lc_link(const uint32_t* __restrict__ nodes,
+                                                 const uint8_t* __restrict__ start, uint32_t m,
+                                                 uint32_t* __restrict__ nxt) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256u;
+  for (uint64_t q = (uint64_t)blockIdx.x * 256u + threadIdx.x; q < m; q += stride) {
+    const uint32_t v = nodes ? nodes[q] : (uint32_t)q;
+    uint32_t nx = kNil;
+    if (q + 1 < m && !start[q + 1]) nx = nodes ? nodes[q + 1] : (uint32_t)(q + 1);
+    nxt[v] = nx;
+  }
+}
+
+// Over rows: row i is slot i, live, with the count and the two ends of its list.
+__global__ __launch_bounds__(256) void k_lc_rows(const uint32_t* __restrict__ off,
+                                                 const uint32_t* __restrict__ nodes, uint32_t n,
+                                                 uint32_t* __restrict__ cnt,
+                                                 uint32_t* __restrict__ head,
+                                                 uint32_t* __restrict__ tail,
+                                                 uint32_t* __restrict__ order) {
+  const uint32_t base = off[0];
+  const uint64_t stride = (uint64_t)gridDim.x * 256u;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += stride) {
+    const uint32_t a = off[i] - base, b = off[i + 1] - base;  // (a < b <= m: checked)
+    cnt[i] = b - a;
+    head[i] = nodes ? nodes[a] : a;
+    tail[i] = nodes ? nodes[b - 1] : b - 1;
+    order[i] = (uint32_t)i;
+  }
+}
+
+void launch_clusters_check_rows(const uint32_t* off, uint32_t n, uint32_t m, uint8_t* start,
+                                unsigned long long* err, hipStream_t s, uint32_t grid_cap) {
+  if (n) k_lc_check_rows<<<res_grid(n, 256, grid_cap), 256, 0, s>>>(off, n, m, start, err);
+}
+
+void launch_clusters_check_nodes(const uint32_t* nodes, uint32_t m, uint32_t members,
+                                 uint32_t* owner, unsigned long long* err, hipStream_t s,
+                                 uint32_t grid_cap) {
+  if (m) k_lc_check_nodes<<<res_grid(m, 256, grid_cap), 256, 0, s>>>(nodes, m, members, owner, err);
+}
+
+void launch_clusters_link(const Rows& r, uint32_t* order, const uint32_t* off,
+                          const uint32_t* nodes, const uint8_t* start, uint32_t n, uint32_t m,
+                          uint32_t members, hipStream_t s, uint32_t grid_cap) {
+  if (members) (void)hipMemsetAsync(r.nxt, 0xFF, sizeof(uint32_t) * (size_t)members, s);
+  if (n == 0) return;
+  k_lc_link<<<res_grid(m, 256, grid_cap), 256, 0, s>>>(nodes, start, m, r.nxt);
+  k_lc_rows<<<res_grid(n, 256, grid_cap), 256, 0, s>>>(off, nodes, n, r.cnt, r.head, r.tail, order);
 }
 
 }  // namespace klsh

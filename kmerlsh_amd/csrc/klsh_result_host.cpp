@@ -150,19 +150,24 @@ int klsh_result(klsh_ctx* ctx, float* rows, uint64_t* member_offsets, uint64_t* 
     return 0;
   }
   if (member_offsets || member_ids) {
-    std::vector<uint32_t> ord(n), head(ctx->slots), nxt(ctx->members);
+    std::vector<uint32_t> ord(n), head(ctx->slots), cnt(ctx->slots), nxt(ctx->members);
     if (n) KLSH_HIP(hipMemcpy(ord.data(), ctx->order, 4 * n, hipMemcpyDeviceToHost));
-    if (ctx->slots)
+    if (ctx->slots) {
       KLSH_HIP(hipMemcpy(head.data(), ctx->rows.head, 4 * ctx->slots, hipMemcpyDeviceToHost));
+      KLSH_HIP(hipMemcpy(cnt.data(), ctx->rows.cnt, 4 * ctx->slots, hipMemcpyDeviceToHost));
+    }
     if (ctx->members)
       KLSH_HIP(hipMemcpy(nxt.data(), ctx->rows.nxt, 4 * ctx->members, hipMemcpyDeviceToHost));
     uint64_t m = 0;
     for (uint64_t i = 0; i < n; ++i) {
       if (member_offsets) member_offsets[i] = m;
       if (ord[i] >= ctx->slots) return fail(KLSH_E_STATE, "corrupt live order");
+      // the caller sized member_ids by klsh_count, the sum of cnt (which may be below the node
+      // count: nodes in no list): a row's walk past its own cnt would write past that buffer
+      uint32_t left = cnt[ord[i]];
       for (uint32_t node = head[ord[i]]; node != klsh::kNil; node = nxt[node]) {
         // every member belongs to exactly one live row: a longer walk is a broken list
-        if (node >= ctx->members || m >= ctx->members)
+        if (node >= ctx->members || m >= ctx->members || left-- == 0)
           return fail(KLSH_E_STATE, "corrupt member list");
         if (member_ids) member_ids[m] = ctx->ids[node];
         ++m;
