@@ -308,6 +308,45 @@ int klsh_result_device(klsh_ctx* ctx, float* d_rows, uint32_t* d_member_offsets,
                        uint32_t* d_member_nodes, uint32_t* d_labels);
 int klsh_labels(klsh_ctx* ctx, uint32_t* labels /* host, M entries */);
 
+/* The cluster files, written from the device: the reference's IOMat::SaveResult
+ * and IOMat::SaveBinary (io/ioMatrix.cc:265-294, 322-351).  For every live row, in klsh_result's
+ * order, whose member count c exceeds ignore_small:
+ *   clust_path  text: decimal(c), then '\t' decimal(id) per member in klsh_result's order, '\n'
+ *               (decimal as ostream << uint64_t prints: no leading zeros, up to 20 digits);
+ *   bin_path    the row's d floats, packed, host byte order.
+ * Either path may be NULL (that file is not produced; both NULL is KLSH_E_ARG); both files are
+ * opened with truncation.  A node that no live row holds is never written.  ignore_small < 0 is
+ * KLSH_E_ARG (the reference's two writers disagree there: one compares size_t > int, the other
+ * int > int).  Refused before any device work and before a file is opened or truncated: the
+ * argument errors, nothing loaded (KLSH_E_STATE), a wrong stats->struct_size, a path that cannot
+ * be opened for writing (KLSH_E_ARG; when only the second path fails the first is untouched).  A
+ * broken member list is KLSH_E_STATE "corrupt member list", as in klsh_result.  A write that
+ * fails later returns KLSH_E_ARG after removing both files.
+ * The member lists come from the list ranking of klsh_result_device; the text is formatted by
+ * kernels and leaves in windows of option "save_chunk_bytes" (default 64 MB; the binary file in
+ * whole rows, one row at least per chunk) through two device and two pinned buffers, a chunk's
+ * copy running beside the previous chunk's fwrite.  The files do not depend on the chunk size.
+ * The ids are uploaded once per call unless the load defined them as base + node
+ * (klsh_load_counts; a NULL member_ids of the other loads).  The call reads the context and
+ * changes none of its state: klsh_result, klsh_row_state and the next klsh_cluster are what they
+ * would have been.  On a context bound to a comm group it writes this rank's replica.  Both
+ * files are complete, and the engine's stream synchronized, when it returns.
+ * Options (test hooks): "save_chunk_bytes" (>= 32; 0 = the default), "save_offset_base" (the
+ * byte position the text scan starts from, in [0, 2^48]; the file does not change); read-only,
+ * of the last call: "save_chunks", "save_ids_uploaded". */
+typedef struct klsh_save_stats {
+  uint64_t struct_size;      /* in: sizeof(klsh_save_stats) */
+  uint64_t clusters;         /* live rows */
+  uint64_t clusters_written, members_written;
+  uint64_t text_bytes, bin_bytes, chunks /* device-to-host chunks, both files */;
+  double rank_ms;    /* offsets + list ranking (the kernels of klsh_result.hip) */
+  double format_ms;  /* HIP-event time of the save kernels (keep, lengths, emit, row gather) */
+  double write_ms;   /* host fwrite */
+  double total_ms;
+} klsh_save_stats;
+int klsh_save_clusters(klsh_ctx* ctx, const char* clust_path, const char* bin_path,
+                       int ignore_small, klsh_save_stats* stats);
+
 /* ---- path functions, exposed for parity tests ------------------------------------------------- */
 /* Hash::LSH::random_projection(row, table) (reference hash/lshash.cc:44-59) for n rows on the
  * GPU: keys[i] = MSB-first sign bits of the h hyperplanes (table: h x d, row-major).  The same

@@ -39,7 +39,7 @@ EXPORTED = (
     "klsh_kmc_info", "klsh_khtable_first", "klsh_bucket_runs", "klsh_row_state",
     "klsh_count_khtable", "klsh_kcount_listing", "klsh_count_kmc",
     "klsh_load_rows_device", "klsh_result_device", "klsh_labels",
-    "klsh_load_clusters_device",
+    "klsh_load_clusters_device", "klsh_save_clusters",
 )
 
 
@@ -161,6 +161,22 @@ class KlshKmcdbStats(_Sized):
     ]
 
 
+class KlshSaveStats(_Sized):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("clusters", ctypes.c_uint64),
+        ("clusters_written", ctypes.c_uint64),
+        ("members_written", ctypes.c_uint64),
+        ("text_bytes", ctypes.c_uint64),
+        ("bin_bytes", ctypes.c_uint64),
+        ("chunks", ctypes.c_uint64),
+        ("rank_ms", ctypes.c_double),
+        ("format_ms", ctypes.c_double),
+        ("write_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+    ]
+
+
 class KlshKhtableStats(_Sized):
     _fields_ = [
         ("struct_size", ctypes.c_uint64),
@@ -207,6 +223,8 @@ def load_library() -> ctypes.CDLL:
                                                      ctypes.c_uint64, _P, _P, ctypes.c_uint64, _P]),
         "klsh_result_device": (ctypes.c_int, [_P, _P, _P, _P, _P]),
         "klsh_labels": (ctypes.c_int, [_P, _P]),
+        "klsh_save_clusters": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int,
+                                              _P]),
         "klsh_load_counts": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64,
                                             ctypes.c_uint64, ctypes.c_int, _P]),
         "klsh_snapshot": (ctypes.c_int, [_P]),
@@ -777,6 +795,18 @@ class Engine:
         _check(self._lib.klsh_result_device(self._ctx, p(rows), p(off), p(nodes), p(labels)),
                "klsh_result_device")
         return rows, off, nodes[: int(off[-1].item())], labels
+
+    def save_clusters(self, clust_path, bin_path=None, ignore_small: int = 5) -> dict:
+        """The reference's two cluster files written from the device (``klsh_save_clusters``):
+        clust_path gets a text line "count<TAB>id..." per live row with more than ignore_small
+        members, bin_path those rows' float32 values; either may be None.  Returns the call's
+        statistics (include/klsh.h klsh_save_stats)."""
+        st = KlshSaveStats()
+        _check(self._lib.klsh_save_clusters(
+            self._ctx, None if clust_path is None else os.fspath(clust_path).encode(),
+            None if bin_path is None else os.fspath(bin_path).encode(), int(ignore_small),
+            ctypes.byref(st)), "klsh_save_clusters")
+        return st.as_dict()
 
     def labels(self) -> np.ndarray:
         """labels[k] = the result row whose member list holds node k (``klsh_labels``), uint32,

@@ -110,17 +110,6 @@ void load_slice(klsh_ctx* ctx, const RowSet& rs, uint64_t a, uint64_t n) {
         "klsh_load_rows");
 }
 
-char* put_u64(char* p, uint64_t v) {
-  char tmp[24];
-  int k = 0;
-  do {
-    tmp[k++] = (char)('0' + v % 10);
-    v /= 10;
-  } while (v);
-  while (k) *p++ = tmp[--k];
-  return p;
-}
-
 // GetInput (io/ioHT.cc:3-19): token `col` (0: the sample, 1: its KMC database name) of every line
 // (std::getline) of a sample list
 std::vector<std::string> sample_paths(const char* path, int col = 0) {
@@ -520,40 +509,22 @@ int main(int argc, char** argv) {
   }
   run_cluster(ctx, min_sim, iters, 1000000, seed, &counter, verbose);  // app/kmerLSH.cc:490
 
-  RowSet fin;
-  fin.d = d;
-  fetch(ctx, d, &fin);
+  uint64_t n_final = 0;
+  check(klsh_count(ctx, &n_final, nullptr), "klsh_count");
 
-  // SaveResult / SaveBinary, ignore_small = 5 (app/kmerLSH.cc:498-499)
+  // SaveResult / SaveBinary, ignore_small = 5 (app/kmerLSH.cc:498-499): formatted on the device
   const std::string clust = out + ".clust";
-  FILE* fc = fopen(clust.c_str(), "wb");
-  FILE* fb = fopen(out.c_str(), "wb");
-  if (!fc || !fb) {
-    perror("output");
+  klsh_save_stats sst{};
+  sst.struct_size = sizeof(sst);
+  if (klsh_save_clusters(ctx, clust.c_str(), out.c_str(), 5, &sst) != KLSH_OK) {
+    fprintf(stderr, "output: %s\n", klsh_last_error());
     return 1;
   }
-  std::vector<char> buf(1 << 22);
-  char* p = buf.data();
-  for (uint64_t i = 0; i < fin.n(); ++i) {
-    const uint64_t a = fin.off[i], e = fin.off[i + 1];
-    if (e - a <= 5) continue;
-    fwrite(fin.rows.data() + i * d, sizeof(float), d, fb);
-    for (uint64_t k = (uint64_t)-1; k == (uint64_t)-1 || k < e; k = (k == (uint64_t)-1) ? a : k + 1) {
-      if ((size_t)(p - buf.data()) > buf.size() - 64) {
-        fwrite(buf.data(), 1, p - buf.data(), fc);
-        p = buf.data();
-      }
-      if (k == (uint64_t)-1) p = put_u64(p, e - a);
-      else {
-        *p++ = '\t';
-        p = put_u64(p, fin.ids[k]);
-      }
-    }
-    *p++ = '\n';
-  }
-  fwrite(buf.data(), 1, p - buf.data(), fc);
-  fclose(fc);
-  fclose(fb);
+  if (verbose)
+    printf("cluster files: %llu clusters, %llu members (%.1f ms: ranking %.1f, formatting %.1f, "
+           "writing %.1f)\n",
+           (unsigned long long)sst.clusters_written, (unsigned long long)sst.members_written,
+           sst.total_ms, sst.rank_ms, sst.format_ms, sst.write_ms);
   int rc = 0;
   if (extracting)
     rc = run_extract(ctx, sample_paths(in1), sample_paths(in2), out, out1, out2, kmer_k,
@@ -562,6 +533,6 @@ int main(int argc, char** argv) {
   const double secs =
       std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   printf("kmerLSH (gfx950) in total takes (secs): %g, clusters: %llu\n", secs,
-         (unsigned long long)fin.n());
+         (unsigned long long)n_final);
   return rc;
 }

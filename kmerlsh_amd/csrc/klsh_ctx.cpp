@@ -543,6 +543,7 @@ int klsh_load_rows(klsh_ctx* ctx, const float* rows, uint64_t n, int d,
   }
   std::vector<uint32_t> cnt(n), head(n), tail(n), nxt(m), ord(n);
   ctx->ids.assign(m, 0);
+  ctx->set_ids_linear(!member_ids, 0);
   for (uint64_t i = 0; i < n; ++i) {
     ord[i] = (uint32_t)i;
     if (member_offsets) {
@@ -604,6 +605,7 @@ int klsh_load_rows_device(klsh_ctx* ctx, const float* d_rows, uint64_t n, int d,
   KLSH_HIP(hipGetLastError());
   ctx->ids.resize(n);
   for (uint64_t i = 0; i < n; ++i) ctx->ids[i] = member_ids ? member_ids[i] : i;
+  ctx->set_ids_linear(!member_ids, 0);
   ctx->slots = n;
   ctx->members = n;
   klsh::launch_shadow_build(ctx->rows, ctx->slots, s);
@@ -723,6 +725,7 @@ int klsh_load_clusters_device(klsh_ctx* ctx, const float* d_rows, uint64_t n, in
   if (!keep) {
     ctx->ids.resize(M);
     for (uint64_t k = 0; k < M; ++k) ctx->ids[k] = member_ids ? member_ids[k] : k;
+    ctx->set_ids_linear(!member_ids, 0);
   }
   ctx->slots = n;
   ctx->members = M;
@@ -773,6 +776,7 @@ int klsh_load_counts(klsh_ctx* ctx, const uint16_t* counts, uint64_t n_total,
   if (rc) return rc;
   ctx->ids.resize(bs);
   for (uint64_t i = 0; i < bs; ++i) ctx->ids[i] = batch_offset + i;
+  ctx->set_ids_linear(true, batch_offset);
   ctx->slots = bs;
   ctx->members = bs;
   klsh::launch_shadow_build(ctx->rows, ctx->slots, s);

@@ -219,6 +219,22 @@ struct ReadBatch {
 
 }  // namespace klsh
 
+namespace klsh {
+
+// klsh_save_clusters' test hooks and what the last call on the context reached (klsh_options.cpp)
+struct SaveHooks {
+  uint64_t chunk_bytes = 0;   // "save_chunk_bytes": bytes per device-to-host chunk (0 = 64 MB)
+  uint64_t offset_base = 0;   // "save_offset_base": the position the text scan starts from
+  uint64_t chunks = 0;        // "save_chunks"
+  uint32_t ids_uploaded = 0;  // "save_ids_uploaded"
+};
+
+// klsh_result_host.cpp: the kernels of klsh_result.hip over the live order (see there)
+int device_result(klsh_ctx* ctx, uint32_t* d_off, uint32_t* d_nodes, uint32_t* d_labels,
+                  uint64_t* total_out);
+
+}  // namespace klsh
+
 struct klsh_ctx {
   using Counters = klsh::Counters;
 
@@ -282,6 +298,12 @@ struct klsh_ctx {
 
   // host
   std::vector<uint64_t> ids;  // member node -> k-mer id
+  // the load defined ids[node] = ids_base + node (klsh_load_counts; a null member_ids of the other
+  // loads): klsh_save_clusters then formats base + node and uploads nothing.  Cleared by a load
+  // that takes explicit ids, kept by a keep-mode klsh_load_clusters_device.
+  bool ids_linear = false;
+  uint64_t ids_base = 0;
+  void set_ids_linear(bool linear, uint64_t base) { ids_linear = linear, ids_base = linear ? base : 0; }
   klsh::Snapshot snap;
 
   // sharded loop: this rank's exchange and its buffers (sized with the slots)
@@ -358,6 +380,8 @@ struct klsh_ctx {
   klsh::KmcHooks kmc;
   // klsh_count_khtable's (klsh_kcount.cpp)
   klsh::KcountHooks kcount;
+  // klsh_save_clusters' (klsh_save.cpp)
+  klsh::SaveHooks save;
 
   ~klsh_ctx() { release(); }
 

@@ -498,6 +498,39 @@ void launch_clusters_link(const Rows& r, uint32_t* order, const uint32_t* off,
                           const uint32_t* nodes, const uint8_t* start, uint32_t n, uint32_t m,
                           uint32_t members, hipStream_t s, uint32_t grid_cap = 0);
 
+// ---- the cluster files (klsh_save.hip) -----------------------------------------
+// off, nodes: the result's n + 1 member offsets and flat node lists (launch_result_emit).  A row
+// is kept when off[i + 1] - off[i] > ignore_small.  Every launch strides over its range on its
+// own and takes option "grid_cap".
+constexpr uint32_t kSaveTile = 256;        // entries per text tile: one token per lane
+constexpr uint32_t kSaveMaxToken = 32;     // header (<= 10 digits), '\t', id (<= 20 digits), '\n'
+constexpr uint32_t kSaveKept = 0;          // hdr (64-bit words): kept rows
+constexpr uint32_t kSaveMembers = 1;       //   their members
+constexpr uint32_t kSaveErr = 2;           //   non-zero: an entry whose node is outside the table
+constexpr uint32_t kSaveHdrWords = 4;
+inline uint64_t save_tiles(uint64_t total) { return (total + kSaveTile - 1) / kSaveTile; }
+// kslot[rank of kept row i] = order[i]; hdr[kSaveKept], hdr[kSaveMembers] (hdr zeroed by the
+// caller).  tsum: result_tiles(n) words.
+void launch_save_keep(const uint32_t* order, const uint32_t* off, uint32_t n, uint32_t ignore_small,
+                      uint32_t* tsum, uint32_t* kslot, unsigned long long* hdr, hipStream_t s,
+                      uint32_t grid_cap = 0);
+// The text's entries: ids (node -> id; null: id = id_base + node) of `members` nodes.
+struct SaveText {
+  const uint32_t* off;
+  const uint32_t* nodes;
+  const uint64_t* ids;
+  uint64_t id_base;
+  uint32_t n, total, members, ignore_small;
+};
+// tpos[t] = pos_base + the bytes of the tokens of entries below t * kSaveTile, t <= save_tiles
+// (tpos[save_tiles] = pos_base + the text's length): three launches, 64-bit sums.
+void launch_save_positions(const SaveText& tx, uint64_t pos_base, uint64_t* tpos,
+                           unsigned long long* hdr, hipStream_t s, uint32_t grid_cap = 0);
+// The bytes at positions [w0, w1) of the text, from tiles [t_lo, t_hi) (every tile that holds one
+// of them), to out[0, w1 - w0) (16-byte aligned).  Nothing outside that range is stored.
+void launch_save_emit(const SaveText& tx, const uint64_t* tpos, uint64_t t_lo, uint64_t t_hi,
+                      uint64_t w0, uint64_t w1, uint8_t* out, hipStream_t s, uint32_t grid_cap = 0);
+
 // Floating-point self test: sqrt_out[i] = sqrtf(a[i]); div_out[i] = a[i] / b[i] as the merge
 // kernels evaluate them.
 void launch_fp_selftest(const float* a, const float* b, uint32_t n, float* sqrt_out,

@@ -118,6 +118,17 @@ const Option kOptions[] = {
     COUNT("kcount_db_chunk_records", kcount.db_chunk_records),
     READONLY("kcount_db_chunks", c->kcount.db_chunks),
     READONLY("kcount_db_prefix_used", c->kcount.db_prefix_used),
+    {"save_chunk_bytes", GET(c->save.chunk_bytes), SET(
+        if (v != 0 && (v < 32 || v > (1ll << 40)))
+          return out_of_range("save_chunk_bytes", "0 or in [32, 2^40]");
+        c->save.chunk_bytes = (uint64_t)v;
+        return 0;)},
+    {"save_offset_base", GET(c->save.offset_base), SET(
+        if (v < 0 || v > (1ll << 48)) return out_of_range("save_offset_base", "in [0, 2^48]");
+        c->save.offset_base = (uint64_t)v;
+        return 0;)},
+    READONLY("save_chunks", c->save.chunks),
+    READONLY("save_ids_uploaded", c->save.ids_uploaded),
     GRID("h16_grid", pp.h16_grid),
     GRID("h16_segcap", pp.segcap),
     GRID("wide_grid", pp.wide_grid),

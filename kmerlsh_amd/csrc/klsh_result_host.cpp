@@ -7,14 +7,17 @@
 
 #include "klsh_ctx.h"
 
+using klsh::device_result;
+
 // ---- the result on the device ---------------------------------------------------
 // The kernels of klsh_result.hip over the live order: d_off (n + 1 member offsets), d_nodes (the
 // member lists as nodes, flat) and d_labels (the live row of each of the M nodes), all device
 // memory, any may be null; *total_out (may be null) = the live rows' members.  Offsets alone
 // need no workspace beyond the tile sums; nodes or labels take the list ranking's 2 x 8 B x M +
 // 4 B x M, allocated here and freed before returning.  Ends with the stream synchronized.
-static int device_result(klsh_ctx* ctx, uint32_t* d_off, uint32_t* d_nodes, uint32_t* d_labels,
-                         uint64_t* total_out) {
+// (klsh_save.cpp takes its lists from here too: declared in klsh_ctx.h)
+int klsh::device_result(klsh_ctx* ctx, uint32_t* d_off, uint32_t* d_nodes, uint32_t* d_labels,
+                        uint64_t* total_out) {
   const uint64_t n = ctx->n_live, M = ctx->members;
   const bool rank = (d_nodes || d_labels) && M;
   const uint32_t cap = ctx->grid_cap;
