@@ -428,6 +428,14 @@ void klsh_kset_destroy(klsh_kset* set);
 int klsh_check_reads(klsh_ctx* ctx, const klsh_kset* set, const char* seq,
                      const uint64_t* read_offsets, uint64_t n_reads, int k, float kmer_vote,
                      uint32_t* hits, uint8_t* flags);
+/* Test hooks of the set.  klsh_kset_find: slots[i] = the slot of the set's table that holds
+ * keys[i], all ones if the set does not hold it (the key all ones is never held); *n_slots (may be
+ * NULL) = the table's slots, a power of two >= 1024 and >= 2 n, a key's home slot being the low
+ * bits of the murmur3 finalizer of the key and the table probed linearly from there.  All arrays
+ * are host memory; the argument checks are klsh_check_reads'.  Read-only option "extract_window":
+ * the k-mer positions per LDS window of the vote kernel. */
+int klsh_kset_find(klsh_ctx* ctx, const klsh_kset* set, const uint64_t* keys, uint64_t n,
+                   uint64_t* slots, uint64_t* n_slots);
 typedef struct klsh_extract_stats {
   uint64_t struct_size; /* in: sizeof(klsh_extract_stats) */
   uint64_t reads, bases, reads_tested, kmers_checked, reads_extracted, abnormal;

@@ -39,7 +39,7 @@ EXPORTED = (
     "klsh_kmc_info", "klsh_khtable_first", "klsh_bucket_runs", "klsh_row_state",
     "klsh_count_khtable", "klsh_kcount_listing", "klsh_count_kmc",
     "klsh_load_rows_device", "klsh_result_device", "klsh_labels",
-    "klsh_load_clusters_device", "klsh_save_clusters",
+    "klsh_load_clusters_device", "klsh_save_clusters", "klsh_kset_find",
 )
 
 
@@ -262,6 +262,7 @@ def load_library() -> ctypes.CDLL:
         "klsh_kset_destroy": (None, [_P]),
         "klsh_check_reads": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_uint64, ctypes.c_int,
                                             ctypes.c_float, _P, _P]),
+        "klsh_kset_find": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _P, _u64p]),
         "klsh_extract_fastq": (ctypes.c_int, [_P, _P, ctypes.c_char_p, ctypes.c_char_p,
                                               ctypes.c_int, ctypes.c_float, _P]),
         "klsh_build_khtable": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
@@ -464,6 +465,16 @@ class KmerSet:
                                           len(seqs), k, ctypes.c_float(kmer_vote), _ptr(hits),
                                           _ptr(flags)), "klsh_check_reads")
         return hits, flags
+
+    def find(self, keys: np.ndarray) -> tuple[np.ndarray, int]:
+        """Where the set's table keeps each key (``klsh_kset_find``, a test hook): (slot per key as
+        uint64, all ones = absent; the table's slot count)."""
+        k = np.ascontiguousarray(keys, np.uint64)
+        slots = np.zeros(k.size, np.uint64)
+        n_slots = ctypes.c_uint64(0)
+        _check(self._lib.klsh_kset_find(self.engine._ctx, self._set, _ptr(k), k.size, _ptr(slots),
+                                        ctypes.byref(n_slots)), "klsh_kset_find")
+        return slots, int(n_slots.value)
 
     def extract_fastq(self, in_path: str, out_path: str, k: int, kmer_vote: float) -> dict:
         """IOFQ::ReadExtract for one sample (host parse + GPU vote + writer)."""

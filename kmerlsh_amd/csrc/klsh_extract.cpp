@@ -649,6 +649,26 @@ int klsh_check_reads(klsh_ctx* ctx, const klsh_kset* ks, const char* seq,
   return KLSH_OK;
 }
 
+// Test hook (tests/test_gpu_kmer_table.py): where the set's table keeps each key.
+int klsh_kset_find(klsh_ctx* ctx, const klsh_kset* ks, const uint64_t* keys, uint64_t n,
+                   uint64_t* slots, uint64_t* n_slots) {
+  if (!ctx || !ks || ks->ctx != ctx || (n && (!keys || !slots)))
+    return set_error(KLSH_E_ARG, "bad argument");
+  if (n_slots) *n_slots = ks->mask + 1;
+  if (n == 0) return KLSH_OK;
+  KLSH_HIP(hipSetDevice(ctx->device));
+  const hipStream_t s = ctx->stream;
+  klsh::DevBuf<uint64_t> dkey, dslot;
+  KLSH_HIP(dkey.alloc(n));
+  KLSH_HIP(dslot.alloc(n));
+  KLSH_HIP(hipMemcpyAsync(dkey, keys, n * 8, hipMemcpyHostToDevice, s));
+  klsh::launch_kset_find(dkey, n, ks->tab, ks->mask, dslot, s, ctx->grid_cap);
+  KLSH_HIP(hipGetLastError());
+  KLSH_HIP(hipMemcpyAsync(slots, dslot, n * 8, hipMemcpyDeviceToHost, s));
+  KLSH_HIP(hipStreamSynchronize(s));
+  return KLSH_OK;
+}
+
 int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
                        const char* out_path, int k, float kmer_vote, klsh_extract_stats* st) {
   if (!ctx || !ks || ks->ctx != ctx || !in_path || !out_path)

@@ -11,6 +11,7 @@
 // memcmp order of the bytes is the order of the byte-swapped word.
 //
 //   k_kset_insert  the set's k-mers as read from kmer_set.hex, into the k-mer table (klsh_kmer.h)
+//   k_kset_find    a test hook (klsh_kset_find): the slot that holds each of the caller's keys
 //   k_check_reads  one wave per read: the read's bases staged as 2-bit codes in LDS (one byte
 //                  each), one lane per k-mer position building its word from LDS, reverse
 //                  complement with bit operations, one probe sequence per lane, a wave sum of the
@@ -28,8 +29,7 @@
 
 namespace klsh {
 
-constexpr int kCheckWaves = 4;        // waves per workgroup, each on its own reads
-constexpr uint32_t kCheckWindow = 2048;  // k-mer positions per LDS window (per wave)
+constexpr int kCheckWaves = 4;  // waves per workgroup, each on its own reads
 
 __global__ __launch_bounds__(256) void k_kset_insert(const uint64_t* __restrict__ kmers, uint64_t n,
                                                      unsigned long long* __restrict__ tab,
@@ -38,6 +38,17 @@ __global__ __launch_bounds__(256) void k_kset_insert(const uint64_t* __restrict_
     const unsigned long long key = kmers[i];
     if (key == kKtabEmpty) continue;  // cannot be a canonical rep: never looked up
     (void)ktab_claim(tab, mask, key);
+  }
+}
+
+// klsh_kset_find (a test hook): slots[i] = the slot that holds keys[i], all ones if none does
+// (all ones itself is the empty mark, never a key)
+__global__ __launch_bounds__(256) void k_kset_find(const uint64_t* __restrict__ keys, uint64_t n,
+                                                   const uint64_t* __restrict__ tab, uint64_t mask,
+                                                   uint64_t* __restrict__ slots) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull) {
+    const uint64_t key = keys[i];
+    slots[i] = key == kKtabEmpty ? kKtabEmpty : ktab_find<true>(tab, mask, key);
   }
 }
 
@@ -107,6 +118,12 @@ void launch_kset_insert(const uint64_t* kmers, uint64_t n, uint64_t* tab, uint64
   if (n == 0) return;
   k_kset_insert<<<stride_grid(n, grid_cap, 8192), 256, 0, s>>>(
       kmers, n, reinterpret_cast<unsigned long long*>(tab), mask);
+}
+
+void launch_kset_find(const uint64_t* keys, uint64_t n, const uint64_t* tab, uint64_t mask,
+                      uint64_t* slots, hipStream_t s, uint32_t grid_cap) {
+  if (n == 0) return;
+  k_kset_find<<<stride_grid(n, grid_cap, 8192), 256, 0, s>>>(keys, n, tab, mask, slots);
 }
 
 void launch_check_reads(const uint8_t* seq, const uint64_t* off, uint64_t n, int k, float vote,

@@ -580,6 +580,10 @@ void launch_min_u32(uint32_t* a, const uint32_t* b, size_t n, hipStream_t s);
 // mode E (klsh_extract.hip): kmers[i] into the set's table (all ones skipped)
 void launch_kset_insert(const uint64_t* kmers, uint64_t n, uint64_t* tab, uint64_t mask,
                         hipStream_t s, uint32_t grid_cap = 0);
+// slots[i] = the slot of keys[i] in the set's table, all ones if it is absent (klsh_kset_find)
+void launch_kset_find(const uint64_t* keys, uint64_t n, const uint64_t* tab, uint64_t mask,
+                      uint64_t* slots, hipStream_t s, uint32_t grid_cap = 0);
+constexpr uint32_t kCheckWindow = 2048;  // k-mer positions per LDS window (per wave)
 // Read r = seq[off[r] .. off[r+1]): hits[r] = its k-mer positions whose canonical k-mer is in the
 // set, flags[r] = hits / (len - k + 1) > vote (float), both 0 for reads shorter than k + 10.
 void launch_check_reads(const uint8_t* seq, const uint64_t* off, uint64_t n, int k, float vote,

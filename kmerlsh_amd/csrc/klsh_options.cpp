@@ -94,6 +94,7 @@ const Option kOptions[] = {
         return 0;)},
     READONLY("kmc_decode_launches", c->kmc.decode_launches),
     READONLY("kmc_high_sort", c->kmc.high_sort),
+    READONLY("extract_window", klsh::kCheckWindow),
     COUNT("kcount_batch_reads", kcount.batch_reads),
     {"kcount_table_slots", GET(c->kcount.table_slots), SET(
         if (v != 0 && (v < 1024 || v > (1ll << 32) || (v & (v - 1))))

@@ -12,7 +12,8 @@ offsets say it must be.  No tolerances: a cache that is off by one ulp is a wron
 Also here: the seeded inputs of the state tests ("spread" single-bucket rows, "ladder" loop rows),
 the projection tests' adversarial rows, the result comparison and the options context manager,
 shared by test_gpu_parity.py, test_gpu_row_state.py, test_gpu_sharded.py,
-test_gpu_launch_geometry.py, test_gpu_widths.py and test_gpu_small_loops.py, and `clustered`,
+test_gpu_launch_geometry.py, test_gpu_widths.py and test_gpu_small_loops.py (the options context
+manager by test_gpu_kmer_table.py too), and `clustered`,
 the seeded group rows of the parity, sharded, width and small-loop tests (the one definition).
 """
 import numpy as np
