@@ -270,8 +270,10 @@ int klsh_set_option(klsh_ctx* ctx, const char* name, int64_t value);
  * image), "last_hash_kernel" (klsh_hash_keys' projection kernel: 0 packed chains, 1 fp16-image
  * screen, 2 f32 fp16x3 wide-row screen, -1 none), "last_hash_variant" (the kernel itself: 0
  * k_project_pk, 1 k_project_wide_pk, 2 k_project_generic, 3 k_project_h16, 4
- * k_project_mfma_wide<512>, 5 k_project_mfma_wide<0>, -1 none) and
- * "last_hash_close_pairs" (its (row, hyperplane) pairs settled by the exact chains). */
+ * k_project_mfma_wide<512>, 5 k_project_mfma_wide<0>, -1 none),
+ * "last_hash_close_pairs" (its (row, hyperplane) pairs settled by the exact chains) and
+ * "tail_local_iters" (the queued iterations of the last klsh_cluster call whose bucket sort was
+ * the top-bits pass + per-bucket LDS sorts of option "tail_local"; 0 where none was queued). */
 int klsh_get_option(klsh_ctx* ctx, const char* name, int64_t* value);
 
 /* ---- results ---------------------------------------------------------------------------------- */
@@ -368,6 +370,23 @@ int klsh_bucket_sort(klsh_ctx* ctx, const uint32_t* keys, uint64_t n, int bits,
  * capacity).  A test hook. */
 int klsh_bucket_runs(klsh_ctx* ctx, const uint32_t* sorted_keys, uint64_t n, int bucket_thr,
                      uint64_t* n_runs, uint32_t* starts, uint32_t* lengths, int32_t* lists);
+/* One queued iteration's bucket order and run lists (run_batched, the iterations below 2^20 rows
+ * whose row count only the device knows), on caller keys.  Every launch is sized for n_max and
+ * reads the real count n_live from device memory; keys[n_live .. n_max) are stale and no kernel
+ * may count, move or overwrite them.  path 1: the top-9-bit partition + the per-bucket LDS sorts
+ * that list the runs (KLSH_E_RANGE unless bits is 10..19); path 0: the LSD passes of `bits` + the
+ * run kernels.  Live keys must be < 2^bits.  1 <= n_live <= n_max < 2^20, 0 <= bits <= 19; all
+ * arrays are host memory.  The sort workspace, the run workspace and the buffers the result may
+ * land in are filled with the byte 0xA5 first (only the run counters start at zero, as in the
+ * loop).  out_keys / out_perm (n_max entries each): the whole result pair, so an entry at or past
+ * n_live is 0xA5A5A5A5 or what the input pair held there (perm starts as 0 .. n_max-1).  n_runs,
+ * starts, lengths, lists: as klsh_bucket_runs.  counters (7, may be NULL): run heads (runs of one
+ * key included), rows in the runs of lists 0..5, in each of lists 6..9, and in list 10.  A test
+ * hook. */
+int klsh_tail_buckets(klsh_ctx* ctx, const uint32_t* keys, uint64_t n_max, uint64_t n_live,
+                      int bits, int bucket_thr, int path, uint32_t* out_keys, uint32_t* out_perm,
+                      uint64_t* n_runs, uint32_t* starts, uint32_t* lengths, int32_t* lists,
+                      uint32_t* counters);
 /* p_cluster (reference function/cluster.cc:56-87) over the loaded rows taken as ONE bucket in
  * load order, at threshold thr.  Afterwards klsh_count/klsh_result give the survivors. */
 int klsh_pcluster(klsh_ctx* ctx, float thr);

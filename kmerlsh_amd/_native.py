@@ -39,7 +39,7 @@ EXPORTED = (
     "klsh_kmc_info", "klsh_khtable_first", "klsh_bucket_runs", "klsh_row_state",
     "klsh_count_khtable", "klsh_kcount_listing", "klsh_count_kmc",
     "klsh_load_rows_device", "klsh_result_device", "klsh_labels",
-    "klsh_load_clusters_device", "klsh_save_clusters", "klsh_kset_find",
+    "klsh_load_clusters_device", "klsh_save_clusters", "klsh_kset_find", "klsh_tail_buckets",
 )
 
 
@@ -240,6 +240,9 @@ def load_library() -> ctypes.CDLL:
         "klsh_row_state": (ctypes.c_int, [_P, _P, _P, _P, _u64p, _u64p]),
         "klsh_bucket_runs": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int, _u64p, _P, _P,
                                             _P]),
+        "klsh_tail_buckets": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, _P, _P, _u64p, _P, _P, _P,
+                                             _P]),
         "klsh_hyperplanes": (ctypes.c_int, [ctypes.c_uint32, _u64p, ctypes.c_int,
                                             ctypes.c_int, _P]),
         "klsh_fp_selftest": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _P, _P]),
@@ -755,6 +758,27 @@ class Engine:
                "klsh_bucket_runs")
         m = nr.value
         return st[:m], ln[:m], li[:m]
+
+    def tail_buckets(self, keys: np.ndarray, n_live: int, bits: int, bucket_thr: int, path: int):
+        """One queued iteration's sort and run listing on caller keys (klsh_tail_buckets): grids
+        for keys.size, the count n_live on the device, path 1 = k_tail_local, 0 = LSD + run
+        kernels.  Returns (keys, perm) of all keys.size entries, (starts, lengths, lists) in start
+        order and the seven counters (heads, small rows, rows of lists 6..9, huge rows)."""
+        k = np.ascontiguousarray(keys, dtype=np.uint32)
+        out = np.zeros_like(k)
+        perm = np.zeros_like(k)
+        cap = k.size + 1  # (a threshold of 0 lists the runs of one row as oversize)
+        st = np.zeros(cap, np.uint32)
+        ln = np.zeros(cap, np.uint32)
+        li = np.zeros(cap, np.int32)
+        ctr = np.zeros(7, np.uint32)
+        nr = ctypes.c_uint64(cap)
+        _check(self._lib.klsh_tail_buckets(self._ctx, _ptr(k), k.size, int(n_live), int(bits),
+                                           int(bucket_thr), int(path), _ptr(out), _ptr(perm),
+                                           ctypes.byref(nr), _ptr(st), _ptr(ln), _ptr(li),
+                                           _ptr(ctr)), "klsh_tail_buckets")
+        m = nr.value
+        return out, perm, (st[:m], ln[:m], li[:m]), ctr
 
     def fp_selftest(self, a: np.ndarray, b: np.ndarray):
         a = np.ascontiguousarray(a, np.float32)

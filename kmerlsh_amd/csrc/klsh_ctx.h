@@ -366,6 +366,9 @@ struct klsh_ctx {
   // top-bits pass + the LDS bucket sort that lists the runs (option "tail_local", default on)
   bool tail_batch = true;
   bool tail_local = true;
+  // queued iterations of the last klsh_cluster call whose sort took that local path (read-only
+  // option "tail_local_iters": counted by the host where run_batched enqueues them)
+  uint64_t tail_local_iters = 0;
   // klsh_hash_keys diagnostics (klsh_get_option): the projection kernel of the last call and
   // the (row, hyperplane) pairs its screen left to the exact chains
   int last_hash_kernel = klsh::kPkNone;

@@ -183,70 +183,173 @@ int klsh_bucket_sort(klsh_ctx* ctx, const uint32_t* keys, uint64_t n, int bits,
   return rc;
 }
 
+// The run lists of one hook call: the lists with the context's own capacities for s positions
+// (klsh_ctx::alloc), the run workspace and the counters (the caller zeroes them), and the read-back.
+struct HookRuns {
+  DevBuf<uint32_t> run_ws;
+  DevBuf<klsh::RunCounters> rc;
+  DevBuf<uint2> huge, over, cls[klsh::kGroupClasses], big[klsh::kBigClasses];
+  klsh::MergePlan plan{};  // the lists of this call, no options
+  klsh::RunCounters hc{};
+
+  int alloc(uint64_t s) {
+    using klsh::kBigClasses;
+    using klsh::kGroupClasses;
+    int e = 0;
+    if ((e = dalloc(rc, 1)) || (e = dalloc(run_ws, klsh::run_ws_words(s))) ||
+        (e = dalloc(huge, s / 897 + 64)) || (e = dalloc(over, s + 64)))
+      return e;
+    for (int c = 0; c < kGroupClasses && !e; ++c) e = dalloc(cls[c], klsh::group_class_capacity(c, s));
+    for (int c = 0; c < kBigClasses && !e; ++c)
+      e = dalloc(big[c], s / ((c ? klsh::kBigRows[c - 1] : 64) + 1) + 64);
+    if (e) return e;
+    plan.run_ws = run_ws;
+    klsh::RunLists& w = plan.lists;
+    w.huge = huge;
+    w.over = over;
+    for (int c = 0; c < kGroupClasses; ++c) w.cls[c] = cls[c];
+    for (int c = 0; c < kBigClasses; ++c) w.big[c] = big[c];
+    w.rc = rc;
+    return 0;
+  }
+
+  // After the listing kernels, on a drained stream: the counters into hc, then every run as
+  // (start, length, list) in start order into the caller's arrays (each may be null).  *n_runs:
+  // in, their capacity; out, the run count.
+  int read_back(uint64_t* n_runs, uint32_t* starts, uint32_t* lengths, int32_t* lists) {
+    using klsh::kBigClasses;
+    using klsh::kGroupClasses;
+    const uint64_t cap = *n_runs;
+    *n_runs = 0;
+    if (hipMemcpy(&hc, rc, sizeof(hc), hipMemcpyDeviceToHost) != hipSuccess)
+      return fail(KLSH_E_HIP, "run counters");
+    std::vector<std::array<uint32_t, 3>> runs;
+    auto take = [&](const uint2* list, uint32_t count, int l) -> int {
+      std::vector<uint2> h(count);
+      if (count && hipMemcpy(h.data(), list, sizeof(uint2) * count, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(KLSH_E_HIP, "list copy");
+      for (const uint2& x : h) runs.push_back({x.x, x.y, (uint32_t)l});
+      return 0;
+    };
+    const klsh::RunLists& w = plan.lists;
+    int e = 0;
+    for (int c = 0; c < kGroupClasses && !e; ++c) e = take(w.cls[c], hc.n_cls[c].v, c);
+    for (int c = 0; c < kBigClasses && !e; ++c) e = take(w.big[c], hc.n_big[c].v, kGroupClasses + c);
+    if (!e) e = take(w.huge, hc.n_huge.v, klsh::kRunListCount - 2);
+    if (!e) e = take(w.over, hc.n_over.v, klsh::kRunListCount - 1);
+    if (e) return e;
+    std::sort(runs.begin(), runs.end());
+    *n_runs = runs.size();
+    if (runs.size() > cap) return fail(KLSH_E_RANGE, "more runs than the output holds (see *n_runs)");
+    for (size_t i = 0; i < runs.size(); ++i) {
+      if (starts) starts[i] = runs[i][0];
+      if (lengths) lengths[i] = runs[i][1];
+      if (lists) lists[i] = (int32_t)runs[i][2];
+    }
+    return 0;
+  }
+};
+
 // The run finding of merge_main alone on caller keys (a test hook): every run of 2+ equal keys
 // of n sorted keys with its list, in start order.
 int klsh_bucket_runs(klsh_ctx* ctx, const uint32_t* sorted_keys, uint64_t n, int bucket_thr,
                      uint64_t* n_runs, uint32_t* starts, uint32_t* lengths, int32_t* lists) {
   if (!ctx || !n_runs || (n && !sorted_keys)) return fail(KLSH_E_ARG, "null argument");
   if (n >= 0xFFFFFFF0ull) return fail(KLSH_E_RANGE, "keys >= 2^32");
-  const uint64_t cap = *n_runs;
-  *n_runs = 0;
-  if (n == 0) return 0;
+  if (n == 0) {
+    *n_runs = 0;
+    return 0;
+  }
   KLSH_HIP(hipSetDevice(ctx->device));
-  using klsh::kBigClasses;
-  using klsh::kGroupClasses;
-  DevBuf<uint32_t> dk, run_ws;
-  DevBuf<klsh::RunCounters> rc;
-  DevBuf<uint2> huge, over, cls[kGroupClasses], big[kBigClasses];
+  DevBuf<uint32_t> dk;
+  HookRuns hr;
   int e = 0;
-  if ((e = dalloc(dk, n)) || (e = dalloc(rc, 1)) || (e = dalloc(run_ws, klsh::run_ws_words(n))) ||
-      (e = dalloc(huge, n / 897 + 64)) || (e = dalloc(over, n / 2 + 64)))
-    return e;
-  for (int c = 0; c < kGroupClasses && !e; ++c) e = dalloc(cls[c], klsh::group_class_capacity(c, n));
-  for (int c = 0; c < kBigClasses && !e; ++c)
-    e = dalloc(big[c], n / ((c ? klsh::kBigRows[c - 1] : 64) + 1) + 64);
-  if (e) return e;
-  klsh::MergePlan plan{};  // the lists of this call, no options
-  plan.run_ws = run_ws;
-  klsh::RunLists& w = plan.lists;
-  w.huge = huge;
-  w.over = over;
-  for (int c = 0; c < kGroupClasses; ++c) w.cls[c] = cls[c];
-  for (int c = 0; c < kBigClasses; ++c) w.big[c] = big[c];
-  w.rc = rc;
+  if ((e = dalloc(dk, n)) || (e = hr.alloc(n))) return e;
   hipStream_t s = ctx->stream;
-  klsh::RunCounters hc{};
   int rc_ = 0;
-  if (hipMemsetAsync(rc, 0, sizeof(hc), s) != hipSuccess ||
+  if (hipMemsetAsync(hr.rc, 0, sizeof(klsh::RunCounters), s) != hipSuccess ||
       hipMemcpyAsync(dk, sorted_keys, 4 * n, hipMemcpyHostToDevice, s) != hipSuccess) {
     rc_ = fail(KLSH_E_HIP, "upload");
   } else {
-    klsh::launch_runs(dk, 0, (uint32_t)n, bucket_thr, plan, klsh::MergeCall{}, s);
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(&hc, rc, sizeof(hc), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
+    klsh::launch_runs(dk, 0, (uint32_t)n, bucket_thr, hr.plan, klsh::MergeCall{}, s);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
       rc_ = fail(KLSH_E_HIP, "run finding");
   }
-  std::vector<std::array<uint32_t, 3>> runs;  // (start, length, list)
-  auto take = [&](const uint2* list, uint32_t count, int l) -> int {
-    std::vector<uint2> h(count);
-    if (count && hipMemcpy(h.data(), list, sizeof(uint2) * count, hipMemcpyDeviceToHost) != hipSuccess)
-      return fail(KLSH_E_HIP, "list copy");
-    for (const uint2& x : h) runs.push_back({x.x, x.y, (uint32_t)l});
-    return 0;
-  };
-  for (int c = 0; c < kGroupClasses && !rc_; ++c) rc_ = take(w.cls[c], hc.n_cls[c].v, c);
-  for (int c = 0; c < kBigClasses && !rc_; ++c) rc_ = take(w.big[c], hc.n_big[c].v, kGroupClasses + c);
-  if (!rc_) rc_ = take(w.huge, hc.n_huge.v, klsh::kRunListCount - 2);
-  if (!rc_) rc_ = take(w.over, hc.n_over.v, klsh::kRunListCount - 1);
-  if (rc_) return rc_;
-  std::sort(runs.begin(), runs.end());
-  *n_runs = runs.size();
-  if (runs.size() > cap) return fail(KLSH_E_RANGE, "more runs than the output holds (see *n_runs)");
-  for (size_t i = 0; i < runs.size(); ++i) {
-    if (starts) starts[i] = runs[i][0];
-    if (lengths) lengths[i] = runs[i][1];
-    if (lists) lists[i] = (int32_t)runs[i][2];
+  (void)hipStreamSynchronize(s);
+  if (rc_) {
+    *n_runs = 0;
+    return rc_;
+  }
+  return hr.read_back(n_runs, starts, lengths, lists);
+}
+
+// One queued iteration's sort and run listing as run_batched's enqueue launches them (a test
+// hook): grids for n_max, the count n_live in device memory, every workspace dirty.
+int klsh_tail_buckets(klsh_ctx* ctx, const uint32_t* keys, uint64_t n_max, uint64_t n_live,
+                      int bits, int bucket_thr, int path, uint32_t* out_keys, uint32_t* out_perm,
+                      uint64_t* n_runs, uint32_t* starts, uint32_t* lengths, int32_t* lists,
+                      uint32_t* counters) {
+  if (!ctx || !n_runs || !keys || !out_keys || !out_perm) return fail(KLSH_E_ARG, "null argument");
+  if (n_live < 1 || n_live > n_max || n_max >= (1ull << 20))
+    return fail(KLSH_E_RANGE, "need 1 <= n_live <= n_max < 2^20");
+  if (bits < 0 || bits > 19) return fail(KLSH_E_RANGE, "bits out of range");
+  if (path != 0 && path != 1) return fail(KLSH_E_RANGE, "path must be 0 or 1");
+  if (path == 1 && !klsh::tail_local_ok((uint32_t)n_max, bits))
+    return fail(KLSH_E_RANGE, "the local path takes keys of 10..19 bits");
+  KLSH_HIP(hipSetDevice(ctx->device));
+  const uint64_t n = n_max, ws_words = klsh::sort_ws_words(n);
+  DevBuf<uint32_t> k0, v0, k1, v1, ws, n_dev;
+  HookRuns hr;
+  int e = 0;
+  if ((e = dalloc(k0, n)) || (e = dalloc(v0, n)) || (e = dalloc(k1, n)) || (e = dalloc(v1, n)) ||
+      (e = dalloc(ws, ws_words)) || (e = dalloc(n_dev, 1)) || (e = hr.alloc(n)))
+    return e;
+  hipStream_t s = ctx->stream;
+  std::vector<uint32_t> iota(n);
+  for (uint64_t i = 0; i < n; ++i) iota[i] = (uint32_t)i;
+  int rc_ = 0;
+  // everything a kernel may read before it wrote it is 0xA5, as after some other iteration; only
+  // the run counters start at zero (each compaction's publisher leaves them so)
+  if (hipMemsetAsync(ws, 0xA5, 4 * ws_words, s) != hipSuccess ||
+      hipMemsetAsync(hr.run_ws, 0xA5, 4 * klsh::run_ws_words(n), s) != hipSuccess ||
+      hipMemsetAsync(k1, 0xA5, 4 * n, s) != hipSuccess ||
+      hipMemsetAsync(v1, 0xA5, 4 * n, s) != hipSuccess ||
+      hipMemsetAsync(hr.rc, 0, sizeof(klsh::RunCounters), s) != hipSuccess ||
+      hipMemsetD32Async(n_dev, (int)(uint32_t)n_live, 1, s) != hipSuccess ||
+      hipMemcpyAsync(k0, keys, 4 * n, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(v0, iota.data(), 4 * n, hipMemcpyHostToDevice, s) != hipSuccess) {
+    rc_ = fail(KLSH_E_HIP, "upload");
+  } else {
+    uint32_t *fk = nullptr, *fv = nullptr;
+    const klsh::MergeCall call{};
+    if (path == 1) {  // (k0, v0) -> (k1, v1) by the top bits, back into (k0, v0) by the low ones
+      const uint32_t* dtot = klsh::radix_sort_top(k0, v0, k1, v1, (uint32_t)n, bits, ws, s,
+                                                  klsh::kNoTime, n_dev);
+      klsh::launch_tail_local(k1, v1, k0, v0, dtot, bits, bucket_thr, hr.plan, call, s);
+      fk = k0;
+      fv = v0;
+    } else {
+      klsh::radix_sort(k0, v0, k1, v1, (uint32_t)n, bits, ws, &fk, &fv, s, klsh::kNoTime, n_dev);
+      klsh::launch_runs(fk, 0, (uint32_t)n, bucket_thr, hr.plan, call, s, n_dev);
+    }
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(out_keys, fk, 4 * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(out_perm, fv, 4 * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      rc_ = fail(KLSH_E_HIP, "tail sort and run listing");
+  }
+  (void)hipStreamSynchronize(s);
+  if (rc_) {
+    *n_runs = 0;
+    return rc_;
+  }
+  if (int e2 = hr.read_back(n_runs, starts, lengths, lists)) return e2;
+  if (counters) {
+    const klsh::RunCounters& c = hr.hc;
+    counters[0] = c.n_seg.v;
+    counters[1] = c.n_small_rows.v;
+    for (int b = 0; b < klsh::kBigClasses; ++b) counters[2 + b] = c.n_big_rows[b].v;
+    counters[2 + klsh::kBigClasses] = c.n_huge_rows.v;
   }
   return 0;
 }

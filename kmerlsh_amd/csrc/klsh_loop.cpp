@@ -345,6 +345,7 @@ static int run_batched(klsh_ctx* ctx, float& threshold, float sim_step, int it, 
       uint32_t *fk = nullptr, *fv = nullptr;
       const bool local = ctx->tail_local && tail_local_ok((uint32_t)n_max, hb);
       const MergeCall call{kt, {nullptr, nullptr}, kNoSink, ctx->grid_cap};
+      ctx->tail_local_iters += local ? 1u : 0u;
       if (local) {  // top-bits partition, then the buckets sorted in LDS with their runs listed
         const uint32_t* dtot = radix_sort_top(ctx->keys, ctx->order, ctx->keys2, ctx->alt,
                                               (uint32_t)n_max, hb, ctx->hist, s, kt, n_dev);
@@ -539,6 +540,7 @@ extern "C" int klsh_cluster(klsh_ctx* ctx, float min_similarity, int iterations,
   st->struct_size = sizeof(*st);
   st->world = (uint64_t)ctx->world();
   ctx->mp.no_counts(), ctx->mp.huge_quiet = 0;  // (the single-device loop sets it per iteration)
+  ctx->tail_local_iters = 0;
   const int run_iters = ctx->stop_after > 0 ? std::min(iterations, ctx->stop_after) : iterations;
   if (ctx->comm)  // any bound group, world 1 included (measures the sharded machinery alone)
     return cluster_sharded(ctx, min_similarity, iterations, run_iters, bucket_size_threshold,

@@ -36,6 +36,9 @@ __device__ __forceinline__ uint32_t* run_counter(RunCounters* rc, int l) {
 
 // The list of a run of b rows (-1: one row).
 __device__ __forceinline__ int run_class(uint32_t b, int bucket_thr) {
+  // one row is in no list under any threshold: at bucket_thr = 0 the tile kernels listed every
+  // such run as oversize (k_tail_local never did), a nested call on one row that draws nothing
+  if (b < 2u) return -1;
   if (bucket_thr >= 0 && b > (uint32_t)bucket_thr) return kRunLists - 1;  // cluster.cc:286
   if (b > 64u) {
     if (b > (uint32_t)kBigRows[kBigClasses - 1]) return kRunLists - 2;

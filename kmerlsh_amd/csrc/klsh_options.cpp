@@ -165,6 +165,7 @@ const Option kOptions[] = {
     READONLY("last_hash_kernel", c->last_hash_kernel),
     READONLY("last_hash_variant", c->last_hash_variant),
     READONLY("last_hash_close_pairs", c->last_hash_close),
+    READONLY("tail_local_iters", c->tail_local_iters),
 };
 
 const Option* find_option(const char* name) {

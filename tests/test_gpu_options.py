@@ -74,7 +74,7 @@ READ_ONLY = {
     "kcount_peak_slots": 0, "kcount_window": 2048, "kcount_db_chunks": 0,
     "kcount_db_prefix_used": -1, "result_rounds": 0, "result_rank_us": 0, "member_nodes": 0,
     "fp16_image": 0, "last_hash_kernel": -1, "last_hash_close_pairs": 0,
-    "last_hash_variant": -1, "extract_window": 2048,
+    "last_hash_variant": -1, "extract_window": 2048, "tail_local_iters": 0,
 }
 
 
@@ -91,7 +91,7 @@ def refused(eng, name, value, pattern):
 
 
 def test_tables_are_complete():
-    assert len(SETTABLE) == 41 and len(READ_ONLY) == 16 and not set(SETTABLE) & set(READ_ONLY)
+    assert len(SETTABLE) == 41 and len(READ_ONLY) == 17 and not set(SETTABLE) & set(READ_ONLY)
 
 
 def test_defaults(eng):

@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, GOLDEN)
 import make_golden_thr  # noqa: E402
 from make_golden_thr import threshold_rows  # noqa: E402
+from bucket_model import runs_reference  # noqa: E402
 from row_state import (adversarial_rows, assert_same_result, clustered, options,  # noqa: E402
                        same_bits)
 
@@ -245,27 +246,6 @@ def test_cluster_variants_agree(engine, oracle, d):
         engine.set_option("tail_batch", 1)
         engine.set_option("projection", 0)
     assert len(set(seen)) == 1, seen
-
-
-def runs_reference(keys, bucket_thr):
-    """Runs of equal keys (the buckets merge_hashtable fills, cluster.cc:15-30) of 2+ rows with the
-    merge step's list: size class by length, > bucket_thr = nestedCluster (cluster.cc:286)."""
-    n = keys.size
-    heads = np.flatnonzero(np.concatenate([[True], keys[1:] != keys[:-1]])) if n else np.zeros(0, int)
-    lens = np.diff(np.concatenate([heads, [n]]))
-    keep = lens >= 2
-    heads, lens = heads[keep], lens[keep]
-    lists = np.empty(lens.size, np.int32)
-    for i, b in enumerate(lens):
-        if bucket_thr >= 0 and b > bucket_thr:
-            lists[i] = 11
-        elif b > 896:
-            lists[i] = 10
-        elif b > 64:
-            lists[i] = 6 + int(np.searchsorted([128, 192, 384, 896], b))
-        else:
-            lists[i] = int(np.searchsorted([2, 4, 8, 16, 32, 64], b))
-    return heads.astype(np.uint32), lens.astype(np.uint32), lists
 
 
 @pytest.mark.parametrize("case", ["random", "giant", "giant_over", "tile_edges", "all_equal",

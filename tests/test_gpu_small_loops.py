@@ -51,9 +51,11 @@ def host_iterations(trace, iters, bthr, d):
     return iters
 
 
-def run(engine, data, want, min_sim, iters, bthr, what, counter=COUNTER, load=True, **opts):
+def run(engine, data, want, min_sim, iters, bthr, what, counter=COUNTER, load=True,
+        local_iters=None, **opts):
     """One klsh_cluster call against the oracle's `want`: trace, counter, result bits, then the
-    cached row state.  Returns the call's statistics."""
+    cached row state; with local_iters, the queued iterations that sorted through k_tail_local
+    (option "tail_local_iters").  Returns the call's statistics."""
     rows, off, ids = data
     with options(engine, **opts):
         if load:
@@ -65,6 +67,9 @@ def run(engine, data, want, min_sim, iters, bthr, what, counter=COUNTER, load=Tr
         assert np.array_equal(trace, want[3]), f"trace differs: {what} {opts}\n{trace}\n{want[3]}"
         assert c == want[4], f"rng_counter {c}, oracle {want[4]}: {what} {opts}"
         check(engine, want, f"{what} {opts}")
+        if local_iters is not None:
+            got = engine.get_option("tail_local_iters")
+            assert got == local_iters, f"tail_local_iters {got}, planned {local_iters}: {what} {opts}"
     return st
 
 
@@ -116,8 +121,13 @@ def test_every_small_n(engine, oracle, d, band):
         assert want[0].shape[0] < n, (n, d, list(want[3]))
         if n <= 8:
             assert 1 in want[3][:-2], (n, d, list(want[3]))
+        # one chunk sized from n: all twelve iterations sort locally from hb = 10 on
+        assert len(want[3]) == 12
+        planned = local_iterations(chunk_plan(want[3], want[0].shape[0], 12)) if d in QUEUED_D else 0
+        assert planned == (12 if d in QUEUED_D and n >= 1024 else 0)
         for opts in A_OPTIONS:
-            run(engine, data, want, 0.8, 12, NO_BTHR, f"n={n} d={d}", **opts)
+            observed = {(): planned, ("tail_local",): 0, ("tail_batch",): 0}.get(tuple(opts))
+            run(engine, data, want, 0.8, 12, NO_BTHR, f"n={n} d={d}", local_iters=observed, **opts)
 
 
 # --------------------------------------------------------- B: calls longer than the ring ------
@@ -145,8 +155,15 @@ def chunk_plan(trace, n_final, iters):
         n_max = int(trace[0]) if c < 2 else n_after[(c - 1) * CHUNK - 1]
         merging = sum(1 for t in range(lo, hi) if n_after[t] < int(trace[t]))
         assert all(int(trace[t]) <= n_max for t in range(lo, hi))
-        plan.append({"n_max": n_max, "hb": floor_log2(n_max), "merging": merging})
+        plan.append({"n_max": n_max, "hb": floor_log2(n_max), "merging": merging,
+                     "count": hi - lo})
     return plan
+
+
+def local_iterations(plan):
+    """The iterations of a fully queued call that sort through k_tail_local under the default
+    options (option "tail_local_iters"): every iteration of the chunks with hb >= 10."""
+    return sum(c["count"] for c in plan if c["hb"] >= LOCAL_HB_MIN)
 
 
 def local_chunks(n, d, iters):
@@ -190,12 +207,18 @@ def test_calls_longer_than_the_ring(engine, oracle, n, d, iters, min_sim):
         # at d = 64 a whole chunk is sized from N = 1: hb = 0, no sort pass, grids of one tile
         assert (plan[-1]["hb"] == 0) == (d == 64), plan
     what = f"n={n} d={d} iters={iters} min_sim={min_sim}"
-    st = run(engine, data, want, min_sim, iters, NO_BTHR, what, hip_events=1)
+    # the sort path of every chunk is observed, not inferred: the engine counts the iterations
+    # it queued with the local sort
+    observed = local_iterations(plan)
+    assert observed == sum(c["count"] for c in plan[:k]) == k * CHUNK
+    st = run(engine, data, want, min_sim, iters, NO_BTHR, what, local_iters=observed, hip_events=1)
     assert st["iterations"] == st["project_launches"] == iters
     assert st["project_timed_launches"] == 0  # every iteration was queued
-    st = run(engine, data, want, min_sim, iters, NO_BTHR, what, hip_events=1, tail_local=0)
+    st = run(engine, data, want, min_sim, iters, NO_BTHR, what, local_iters=0, hip_events=1,
+             tail_local=0)
     assert st["project_timed_launches"] == 0
-    st = run(engine, data, want, min_sim, iters, NO_BTHR, what, hip_events=1, tail_batch=0)
+    st = run(engine, data, want, min_sim, iters, NO_BTHR, what, local_iters=0, hip_events=1,
+             tail_batch=0)
     assert st["project_timed_launches"] == iters  # every iteration host-driven and timed
 
 
