@@ -409,6 +409,21 @@ int klsh_hyperplanes(uint32_t seed_base, uint64_t* rng_counter, int h, int d, fl
 int klsh_fp_selftest(klsh_ctx* ctx, const float* a, const float* b, uint64_t n, float* sqrt_out,
                      float* div_out);
 
+/* The cluster-text parser of klsh_diff_ksets alone (mode E below; a test hook):
+ * `text` (len bytes, host memory) as <F>.clust.  path 0 = as
+ * klsh_diff_ksets chooses, 1 = the host parser, 2 = the kernels only (KLSH_E_ARG on an irregular
+ * text, or one of 2^32 bytes or more).  *n_lines = the text's lines; counts (n_lines), offsets
+ * (n_lines + 1, offsets[c] = the declared counts before line c) and ids (offsets[n_lines]) may all
+ * three be NULL for a size query; *n_ids: in, the capacity of ids; out, the entries (KLSH_E_RANGE
+ * if the capacity is too small; KLSH_E_RANGE with *n_ids = 2^32 when they sum to 2^32 or more,
+ * nothing of that size having been allocated).  *irregular_at = the smallest byte offset that
+ * makes the text irregular — a byte outside the grammar, or the first digit of a run of 19 or
+ * more — all ones if none does.  *path_used: 0 = kernels, 1 = host.  Every array is host memory;
+ * every out-pointer but the three arrays is required. */
+int klsh_parse_clust(klsh_ctx* ctx, const char* text, uint64_t len, int path, uint64_t* n_lines,
+                     uint64_t* counts, uint64_t* offsets, uint64_t* ids, uint64_t* n_ids,
+                     uint64_t* irregular_at, int* path_used);
+
 /* ---- mode E: differential k-mers and read extraction (reference app/kmerLSH.cc:521-580) ------- */
 /* AB::WRS (reference function/funcAB.cc:73-109) for every cluster at once: a cluster with more than
  * size_thresh members (member_counts[c]) is tested with ALGLIB's pooled two-sample Student t-test
@@ -468,6 +483,42 @@ typedef struct klsh_extract_stats {
 int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* set, const char* in_path,
                        const char* out_path, int k, float kmer_vote, klsh_extract_stats* stats);
 
+/* The first half of mode E on the device (reference app/kmerLSH.cc:541-585,
+ * IOMat::ReadClusterAll io/ioMatrix.cc:48-119, AB::WRS): the cluster files to the two differential
+ * k-mer sets.  clust_path is <F>, fp32 rows of d = n1 + n2 values; the member lists are the text
+ * <F>.clust; kmer_set_path holds kmap_size 8-byte k-mer images (kmer_set.hex).
+ *   line_cnt = size(<F>) / (4 d), 0 when d = 0.  The text's lines are getline's (an unterminated,
+ *   non-empty last line counts) and must be line_cnt many: otherwise KLSH_E_ARG.
+ *   A line is parsed as the reference's strtol chain: the first strtol gives n, the declared member
+ *   count; up to n further strtol results are its ids, missing ones are 0, tokens past n are
+ *   ignored.  klsh_wrs runs with member_counts[c] = n.  The ids < kmap_size of a group-1 cluster
+ *   mark A, of a group-2 cluster B; row i of kmer_set.hex goes to A if marked A, else to B if
+ *   marked B.  Each table has the capacity klsh_kset_create gives that many keys, each set is bound
+ *   to ctx (klsh_kset_find, klsh_check_reads, klsh_extract_fastq take it unchanged).
+ * A text of digits, newlines and the other five isspace bytes (9, 11, 12, 13, 32) whose digit runs
+ * are at most 18 long is REGULAR and is parsed by kernels (parse_path 0); any other text, and a
+ * text of 2^32 bytes or more, is parsed whole by the host's strtol code (parse_path 1).  The text
+ * and kmer_set.hex go up through two pinned buffers in chunks of option "diff_chunk_bytes"
+ * (default 64 MB; a test hook, >= 32; 0 = default), the read of a chunk beside the copy of the one
+ * before; no result depends on it.  Read-only option "diff_tile_bytes": the parser's tile.
+ * Both sets are created or neither (*set_a = *set_b = NULL on any error).  Before any device work,
+ * KLSH_E_ARG: NULL arguments, n1 or n2 < 0, a wrong stats->struct_size, an unreadable file, a
+ * kmer_set.hex shorter than 8 kmap_size bytes.  KLSH_E_RANGE, before anything of that size is
+ * allocated: declared counts that sum (saturating) to 2^32 or more.  The call reads nothing of,
+ * and changes nothing in, the context's loaded rows.  stats may be NULL. */
+typedef struct klsh_diff_stats {
+  uint64_t struct_size;            /* in: sizeof(klsh_diff_stats) */
+  uint64_t clusters, entries, text_bytes, tokens;
+  uint64_t tested;                 /* clusters with more than size_thresh members */
+  uint64_t clusters_a, clusters_b; /* group 1 / group 2 */
+  uint64_t ids_a, ids_b;           /* distinct ids < kmap_size per group: the two numbers the CLI prints */
+  uint64_t kmers_a, kmers_b;       /* rows of kmer_set.hex claimed into each set */
+  uint64_t parse_path;             /* 0 device, 1 host */
+  double read_ms, parse_ms /* HIP events */, wrs_ms, select_ms /* HIP events */, total_ms;
+} klsh_diff_stats;
+int klsh_diff_ksets(klsh_ctx* ctx, const char* clust_path, const char* kmer_set_path,
+                    uint64_t kmap_size, int n1, int n2, float pvalue_thresh, int size_thresh,
+                    klsh_kset** set_a, klsh_kset** set_b, klsh_diff_stats* stats);
 /* ---- mode B: the k-mer table of KMC databases (reference io/ioHT.cc:83-199, kmc = false) ------- */
 /* buildKHtable over KMC databases (KMC1 or KMC2/3 layout, <name>.kmc_pre / <name>.kmc_suf, listing
  * as kmer/kmc_api/kmc_file.cpp:66-532): the union of canonical k-mers over the samples, each

@@ -40,6 +40,7 @@ EXPORTED = (
     "klsh_count_khtable", "klsh_kcount_listing", "klsh_count_kmc",
     "klsh_load_rows_device", "klsh_result_device", "klsh_labels",
     "klsh_load_clusters_device", "klsh_save_clusters", "klsh_kset_find", "klsh_tail_buckets",
+    "klsh_diff_ksets", "klsh_parse_clust",
 )
 
 
@@ -177,6 +178,29 @@ class KlshSaveStats(_Sized):
     ]
 
 
+class KlshDiffStats(_Sized):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint64),
+        ("clusters", ctypes.c_uint64),
+        ("entries", ctypes.c_uint64),
+        ("text_bytes", ctypes.c_uint64),
+        ("tokens", ctypes.c_uint64),
+        ("tested", ctypes.c_uint64),
+        ("clusters_a", ctypes.c_uint64),
+        ("clusters_b", ctypes.c_uint64),
+        ("ids_a", ctypes.c_uint64),
+        ("ids_b", ctypes.c_uint64),
+        ("kmers_a", ctypes.c_uint64),
+        ("kmers_b", ctypes.c_uint64),
+        ("parse_path", ctypes.c_uint64),
+        ("read_ms", ctypes.c_double),
+        ("parse_ms", ctypes.c_double),
+        ("wrs_ms", ctypes.c_double),
+        ("select_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+    ]
+
+
 class KlshKhtableStats(_Sized):
     _fields_ = [
         ("struct_size", ctypes.c_uint64),
@@ -268,6 +292,11 @@ def load_library() -> ctypes.CDLL:
         "klsh_kset_find": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _P, _u64p]),
         "klsh_extract_fastq": (ctypes.c_int, [_P, _P, ctypes.c_char_p, ctypes.c_char_p,
                                               ctypes.c_int, ctypes.c_float, _P]),
+        "klsh_diff_ksets": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                           ctypes.POINTER(_P), ctypes.POINTER(_P), _P]),
+        "klsh_parse_clust": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int, _u64p, _P, _P,
+                                            _P, _u64p, _u64p, ctypes.POINTER(ctypes.c_int)]),
         "klsh_build_khtable": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
                                               ctypes.c_int, ctypes.c_char_p, _P]),
         "klsh_cuckoo_order": (ctypes.c_int, [_P, ctypes.c_uint64, ctypes.c_int, _P]),
@@ -445,6 +474,16 @@ class KmerSet:
             _check(err.value or -2, "klsh_kset_create")
         self.size = k.size
 
+    @classmethod
+    def adopt(cls, engine: "Engine", handle, size: int) -> "KmerSet":
+        """A set around a ``klsh_kset*`` the library made on `engine` (``klsh_diff_ksets``); the
+        object owns the handle from here on.  `size`: the keys it was built from."""
+        ks = cls.__new__(cls)  # (no klsh_kset_create: the library made the set)
+        ks._lib, ks.engine = engine._lib, engine
+        ks._set = handle
+        ks.size = int(size)
+        return ks
+
     def close(self) -> None:
         if getattr(self, "_set", None):
             self._lib.klsh_kset_destroy(self._set)
@@ -486,6 +525,49 @@ class KmerSet:
                                             out_path.encode(), k, ctypes.c_float(kmer_vote),
                                             ctypes.byref(st)), "klsh_extract_fastq")
         return st.as_dict()
+
+
+def diff_ksets(engine: "Engine", clust_path: str, kmer_set_path: str, kmap: int, n1: int, n2: int,
+               pval: float, size_thresh: int) -> tuple[KmerSet, KmerSet, dict]:
+    """The cluster files <clust_path> / <clust_path>.clust to the two differential k-mer sets
+    (``klsh_diff_ksets``): (set A, set B, statistics)."""
+    lib = engine._lib
+    a, b = _P(), _P()
+    st = KlshDiffStats()
+    _check(lib.klsh_diff_ksets(engine._ctx, os.fsencode(clust_path), os.fsencode(kmer_set_path),
+                               int(kmap), int(n1), int(n2), ctypes.c_float(pval), int(size_thresh),
+                               ctypes.byref(a), ctypes.byref(b), ctypes.byref(st)),
+           "klsh_diff_ksets")
+    return (KmerSet.adopt(engine, a.value, st.kmers_a), KmerSet.adopt(engine, b.value, st.kmers_b),
+            st.as_dict())
+
+
+def parse_clust(engine: "Engine", text: bytes, path: int = 0, ids: bool = True) -> dict:
+    """``klsh_parse_clust`` (a test hook): the text of a .clust file parsed by the kernels
+    (path 2), the host parser (1) or whichever ``klsh_diff_ksets`` would take (0).  Returns
+    n_lines, n_ids, irregular_at (None if the text is regular), path_used and, with `ids`, counts,
+    offsets and ids (uint64 arrays); without, the size query alone."""
+    lib = engine._lib
+    buf = np.frombuffer(bytes(text) + b"\0", np.uint8)
+    n_lines, n_ids, irr = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    used = ctypes.c_int(-1)
+
+    def call(counts, offsets, idv):
+        _check(lib.klsh_parse_clust(engine._ctx, _ptr(buf), len(text), int(path),
+                                    ctypes.byref(n_lines), _ptr(counts), _ptr(offsets), _ptr(idv),
+                                    ctypes.byref(n_ids), ctypes.byref(irr), ctypes.byref(used)),
+               "klsh_parse_clust")
+
+    call(None, None, None)
+    out = {}
+    if ids:
+        nl, ni = n_lines.value, n_ids.value  # (one entry at least: no empty array's NULL pointer)
+        counts, offsets, idv = (np.zeros(max(n, 1), np.uint64) for n in (nl, nl + 1, ni))
+        call(counts, offsets, idv)
+        out.update(counts=counts[:nl], offsets=offsets[:nl + 1], ids=idv[:ni])
+    out.update(n_lines=int(n_lines.value), n_ids=int(n_ids.value), path_used=int(used.value),
+               irregular_at=None if irr.value == 2**64 - 1 else int(irr.value))
+    return out
 
 
 class Engine:

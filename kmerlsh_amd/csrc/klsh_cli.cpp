@@ -207,65 +207,21 @@ int run_extract(klsh_ctx* ctx, const std::vector<std::string>& s1,
                 const std::vector<std::string>& s2, const std::string& clust_file,
                 const std::string& out1, const std::string& out2, int k, int size_thresh,
                 float pval, float vote, bool verbose) {
-  const int n1 = (int)s1.size(), n2 = (int)s2.size(), d = n1 + n2;
+  const int n1 = (int)s1.size(), n2 = (int)s2.size();
   if (verbose) printf("Start to extract the differential reads from raw data\n");
-  // IOMat::ReadClusterAll: centroid rows of <F>, member lists of <F>.clust, paired line by line
-  FILE* fb = fopen(clust_file.c_str(), "rb");
-  if (!fb) {
-    printf("Error! file ( %s ) not open!\n", clust_file.c_str());
-    return 1;
-  }
-  fseek(fb, 0, SEEK_END);
-  const uint64_t line_cnt = d > 0 ? (uint64_t)ftell(fb) / (sizeof(float) * d) : 0;
-  fseek(fb, 0, SEEK_SET);
-  std::vector<float> values(line_cnt * (uint64_t)d);
-  if (line_cnt && fread(values.data(), sizeof(float) * d, line_cnt, fb) != line_cnt) {
-    fprintf(stderr, "kmerLSH: short read of %s\n", clust_file.c_str());
-    return 1;
-  }
-  fclose(fb);
+  // IOMat::ReadClusterAll, AB::WRS and the two k-mer sets in one library call (klsh_diff_ksets):
+  // centroid rows of <F>, member lists of <F>.clust, paired line by line; the distinct ids per
+  // group are the reference's two unordered_sets, and a k-mer goes to A if its id is in A's set,
+  // else to B if in B's (app/kmerLSH.cc:565-571)
   const std::string cf = clust_file + ".clust";
-  FILE* fc = fopen(cf.c_str(), "rb");
-  if (!fc) {
-    printf("Error! file ( %s ) not open!\n", cf.c_str());
-    return 1;
-  }
-  std::vector<uint64_t> counts, ids, off{0};
-  {
-    std::string line;
-    int c;
-    auto parse = [&]() {  // strtol chain: n, then up to n ids, missing ones stay 0
-      const char* p = line.c_str();
-      char* e = nullptr;
-      const uint64_t n = (uint64_t)strtol(p, &e, 10);
-      uint64_t got = 0;
-      std::vector<uint64_t> v(n, 0);
-      while (p != e && got < n) {
-        p = e;
-        v[got++] = (uint64_t)strtol(p, &e, 10);
-      }
-      counts.push_back(n);
-      ids.insert(ids.end(), v.begin(), v.end());
-      off.push_back(ids.size());
-      line.clear();
-    };
-    bool any = false;
-    while ((c = fgetc(fc)) != EOF) {
-      any = true;
-      if (c == '\n') parse();
-      else line.push_back((char)c);
+  for (const std::string* path : {&clust_file, &cf}) {
+    FILE* f = fopen(path->c_str(), "rb");
+    if (!f) {
+      printf("Error! file ( %s ) not open!\n", path->c_str());
+      return 1;
     }
-    if (any && !line.empty()) parse();
-    fclose(fc);
+    fclose(f);
   }
-  if (counts.size() != line_cnt) {
-    fprintf(stderr, "kmerLSH: %s has %zu clusters, %s %llu rows (the reference requires equal)\n",
-            cf.c_str(), counts.size(), clust_file.c_str(), (unsigned long long)line_cnt);
-    return 1;
-  }
-  std::vector<uint8_t> group(line_cnt);
-  check(klsh_wrs(values.data(), line_cnt, n1, n2, counts.data(), pval, size_thresh, group.data()),
-        "klsh_wrs");
   // kmer_count.log: kmap_size; kmer_set.hex: kmap_size k-mers of 8 bytes (Kmer::writeBytes)
   FILE* lf = fopen("kmer_count.log", "r");
   unsigned long long kmap = 0;
@@ -274,36 +230,18 @@ int run_extract(klsh_ctx* ctx, const std::vector<std::string>& s1,
     return 1;
   }
   fclose(lf);
-  // distinct ids per group (the reference's two unordered_sets); a k-mer goes to A if its id is in
-  // A's set, else to B if in B's (app/kmerLSH.cc:565-571)
-  std::vector<uint8_t> in1(kmap, 0), in2(kmap, 0);
-  uint64_t na = 0, nb = 0;
-  for (uint64_t c = 0; c < line_cnt; ++c)
-    for (uint64_t q = off[c]; q < off[c + 1]; ++q) {
-      if (ids[q] >= kmap) continue;
-      if (group[c] == 1 && !in1[ids[q]]) in1[ids[q]] = 1, na += 1;
-      if (group[c] == 2 && !in2[ids[q]]) in2[ids[q]] = 1, nb += 1;
-    }
-  if (verbose) {
-    printf("# of differential kmers in group A : %llu\n", (unsigned long long)na);
-    printf("# of differential kmers in group B : %llu\n", (unsigned long long)nb);
-  }
-  std::vector<uint64_t> kmers(kmap), k1, k2;
-  FILE* kf = fopen("kmer_set.hex", "rb");
-  if (!kf || fread(kmers.data(), 8, kmap, kf) != kmap) {
-    fprintf(stderr, "kmerLSH: kmer_set.hex unreadable\n");
+  klsh_kset *set1 = nullptr, *set2 = nullptr;
+  klsh_diff_stats ds{};
+  ds.struct_size = sizeof(ds);
+  if (klsh_diff_ksets(ctx, clust_file.c_str(), "kmer_set.hex", kmap, n1, n2, pval, size_thresh,
+                      &set1, &set2, &ds) != KLSH_OK) {
+    fprintf(stderr, "kmerLSH: %s\n", klsh_last_error());
     return 1;
   }
-  fclose(kf);
-  for (uint64_t i = 0; i < kmap; ++i) {
-    if (in1[i]) k1.push_back(kmers[i]);
-    else if (in2[i]) k2.push_back(kmers[i]);
+  if (verbose) {
+    printf("# of differential kmers in group A : %llu\n", (unsigned long long)ds.ids_a);
+    printf("# of differential kmers in group B : %llu\n", (unsigned long long)ds.ids_b);
   }
-  int err = 0;
-  klsh_kset* set1 = klsh_kset_create(ctx, k1.data(), k1.size(), &err);
-  check(err, "klsh_kset_create");
-  klsh_kset* set2 = klsh_kset_create(ctx, k2.data(), k2.size(), &err);
-  check(err, "klsh_kset_create");
   for (int g = 0; g < 2; ++g) {  // IOFQ::Extracting per group
     const auto& ss = g == 0 ? s1 : s2;
     const std::string& pre = g == 0 ? out1 : out2;

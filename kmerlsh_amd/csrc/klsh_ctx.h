@@ -229,6 +229,11 @@ struct SaveHooks {
   uint32_t ids_uploaded = 0;  // "save_ids_uploaded"
 };
 
+// klsh_diff_ksets' test hook (klsh_options.cpp)
+struct DiffHooks {
+  uint64_t chunk_bytes = 0;  // "diff_chunk_bytes": bytes per host-to-device chunk (0 = 64 MB)
+};
+
 // klsh_result_host.cpp: the kernels of klsh_result.hip over the live order (see there)
 int device_result(klsh_ctx* ctx, uint32_t* d_off, uint32_t* d_nodes, uint32_t* d_labels,
                   uint64_t* total_out);
@@ -385,6 +390,8 @@ struct klsh_ctx {
   klsh::KcountHooks kcount;
   // klsh_save_clusters' (klsh_save.cpp)
   klsh::SaveHooks save;
+  // klsh_diff_ksets' (klsh_diff.cpp)
+  klsh::DiffHooks diff;
 
   ~klsh_ctx() { release(); }
 
@@ -466,4 +473,13 @@ struct klsh_ctx {
   int check_device_err() const;
   // p must be memory of this context's device (the device entry points' pointer arguments).
   int check_device_ptr(const void* p, const char* what) const;
+};
+
+// A differential k-mer set (klsh_kset_create in klsh_extract.cpp, klsh_diff_ksets in
+// klsh_diff.cpp): the k-mer table of klsh_kmer.h, `mask + 1` slots, built from n keys.
+struct klsh_kset {
+  klsh_ctx* ctx = nullptr;
+  klsh::DevBuf<uint64_t> tab;
+  uint64_t mask = 0;
+  uint64_t n = 0;
 };

@@ -190,6 +190,19 @@ __device__ __forceinline__ void link_members(const Rows& r, uint32_t cur, uint32
   r.cnt[cur] = 0;
 }
 
+// The row of entry q of a flat list (klsh_save.hip's live rows, klsh_diff.hip's text lines): the
+// largest i in [lo, hi] with off[i] <= q (rows without members share their offset with the next
+// row, which the search passes over)
+__device__ __forceinline__ uint32_t row_of(const uint32_t* __restrict__ off, uint32_t lo,
+                                           uint32_t hi, uint32_t q) {
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+    if (off[mid] <= q) lo = mid;
+    else hi = mid - 1u;
+  }
+  return lo;
+}
+
 // =============================================================================== scans ==========
 // 256-lane exclusive scan; returns the lane's exclusive prefix, *total = block sum.
 __device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t* total) {

@@ -516,13 +516,6 @@ struct klsh_fastq {
   FastqReader r;
 };
 
-struct klsh_kset {
-  klsh_ctx* ctx = nullptr;
-  klsh::DevBuf<uint64_t> tab;
-  uint64_t mask = 0;
-  uint64_t n = 0;
-};
-
 extern "C" {
 
 int klsh_ttest2(const double* x, int64_t n, const double* y, int64_t m, double* bothtails,

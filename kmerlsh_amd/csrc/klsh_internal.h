@@ -531,6 +531,60 @@ void launch_save_positions(const SaveText& tx, uint64_t pos_base, uint64_t* tpos
 void launch_save_emit(const SaveText& tx, const uint64_t* tpos, uint64_t t_lo, uint64_t t_hi,
                       uint64_t w0, uint64_t w1, uint8_t* out, hipStream_t s, uint32_t grid_cap = 0);
 
+// ---- the cluster files read back (klsh_diff.hip) --------------------------------
+// The text of <F>.clust on the device: len < 2^32 bytes in a buffer of diff_text_alloc(len) bytes,
+// every byte from len on a newline, so that a tile's 16-byte loads and a token's look-ahead are
+// unconditional and in bounds.  Every launch strides over its tiles on its own and takes option
+// "grid_cap".
+constexpr uint32_t kDiffTile = 256 * 16;  // bytes per text tile: 16 aligned bytes per lane
+constexpr uint32_t kDiffPad = 32;         // newline bytes past the last tile, at least
+constexpr uint32_t kDiffMaxDigits = 18;   // a longer digit run makes the text irregular
+constexpr uint32_t kDiffLineTile = 256;   // lines / entries per tile of the later passes
+inline uint64_t diff_tiles(uint64_t len) { return (len + kDiffTile - 1) / kDiffTile; }
+inline uint64_t diff_text_alloc(uint64_t len) { return diff_tiles(len) * kDiffTile + kDiffPad; }
+inline uint64_t diff_line_tiles(uint64_t n) { return (n + kDiffLineTile - 1) / kDiffLineTile; }
+// hdr (64-bit words; the caller sets hdr[kDiffIrregular] to all ones and zeroes the rest)
+constexpr uint32_t kDiffIrregular = 0;  // the smallest offset that makes the text irregular
+constexpr uint32_t kDiffNewlines = 1;
+constexpr uint32_t kDiffTokens = 2;     // maximal digit runs
+constexpr uint32_t kDiffLines = 3;      // newlines, + 1 for an unterminated last line
+constexpr uint32_t kDiffEntries = 4;    // the declared counts' sum, saturating at kDiffSat
+constexpr uint32_t kDiffIdsA = 5, kDiffIdsB = 6, kDiffKmersA = 7, kDiffKmersB = 8;
+constexpr uint32_t kDiffHdrWords = 16;
+constexpr uint64_t kDiffSat = 1ull << 62;
+// per tile: newlines, token starts (tile_nl, tile_ts: diff_tiles(len) words each), the smallest
+// irregular offset; then their exclusive prefixes in place and hdr[kDiffNewlines .. kDiffLines]
+void launch_diff_scan(const uint8_t* txt, uint32_t len, uint32_t* tile_nl, uint32_t* tile_ts,
+                      unsigned long long* hdr, hipStream_t s, uint32_t grid_cap = 0);
+// tok_val[t] = the value of token t (n_tokens of them), line_tok0[l] = the tokens before line l
+// (n_lines + 1 entries): only for a regular text
+void launch_diff_tokens(const uint8_t* txt, uint32_t len, const uint32_t* tile_nl,
+                        const uint32_t* tile_ts, uint32_t n_lines, uint32_t n_tokens,
+                        uint64_t* tok_val, uint32_t* line_tok0, hipStream_t s, uint32_t grid_cap = 0);
+// cnt[c] = line c's first token (0 without one); csum[t] = the saturating sum of the counts of the
+// lines before tile t, t <= diff_line_tiles(n_lines); hdr[kDiffEntries] = the whole sum
+void launch_diff_counts(const uint64_t* tok_val, const uint32_t* line_tok0, uint32_t n_lines,
+                        uint64_t* cnt, uint64_t* csum, unsigned long long* hdr, hipStream_t s,
+                        uint32_t grid_cap = 0);
+// off[c] = the counts before line c, c <= n_lines (only when their sum is below 2^32)
+void launch_diff_offsets(const uint64_t* cnt, const uint64_t* csum, uint32_t n_lines, uint32_t* off,
+                         hipStream_t s, uint32_t grid_cap = 0);
+// ids[q], q < total = off[n_lines]: entry j of line c is the line's token 1 + j, 0 past its tokens
+void launch_diff_ids(const uint64_t* tok_val, const uint32_t* line_tok0, const uint32_t* off,
+                     uint32_t n_lines, uint32_t total, uint64_t* ids, hipStream_t s,
+                     uint32_t grid_cap = 0);
+// mark_a[id] = 1 / mark_b[id] = 1 for the ids < kmap of the entries of group-1 / group-2 lines
+void launch_diff_mark(const uint32_t* off, uint32_t n_lines, const uint64_t* ids, uint32_t total,
+                      const uint8_t* group, uint64_t kmap, uint8_t* mark_a, uint8_t* mark_b,
+                      hipStream_t s, uint32_t grid_cap = 0);
+// hdr[kDiffIdsA ..] += the marks of each set, and the rows each set takes (A first)
+void launch_diff_count(const uint8_t* mark_a, const uint8_t* mark_b, uint64_t kmap,
+                       unsigned long long* hdr, hipStream_t s, uint32_t grid_cap = 0);
+// row i of kmers (the images of kmer_set.hex) into table A if marked A, else into B if marked B
+void launch_diff_insert(const uint64_t* kmers, const uint8_t* mark_a, const uint8_t* mark_b,
+                        uint64_t kmap, uint64_t* tab_a, uint64_t mask_a, uint64_t* tab_b,
+                        uint64_t mask_b, hipStream_t s, uint32_t grid_cap = 0);
+
 // Floating-point self test: sqrt_out[i] = sqrtf(a[i]); div_out[i] = a[i] / b[i] as the merge
 // kernels evaluate them.
 void launch_fp_selftest(const float* a, const float* b, uint32_t n, float* sqrt_out,

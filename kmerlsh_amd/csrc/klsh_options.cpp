@@ -128,6 +128,12 @@ const Option kOptions[] = {
         if (v < 0 || v > (1ll << 48)) return out_of_range("save_offset_base", "in [0, 2^48]");
         c->save.offset_base = (uint64_t)v;
         return 0;)},
+    {"diff_chunk_bytes", GET(c->diff.chunk_bytes), SET(
+        if (v != 0 && (v < 32 || v > (1ll << 40)))
+          return out_of_range("diff_chunk_bytes", "0 or in [32, 2^40]");
+        c->diff.chunk_bytes = (uint64_t)v;
+        return 0;)},
+    READONLY("diff_tile_bytes", klsh::kDiffTile),
     READONLY("save_chunks", c->save.chunks),
     READONLY("save_ids_uploaded", c->save.ids_uploaded),
     GRID("h16_grid", pp.h16_grid),

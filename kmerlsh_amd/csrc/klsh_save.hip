@@ -64,18 +64,6 @@ __device__ __forceinline__ void put_dec(uint8_t* p, uint64_t v, uint32_t nd) {
   }
 }
 
-// the live row of entry q: the largest i in [lo, hi] with off[i] <= q (rows without members share
-// their offset with the next row, which the search passes over)
-__device__ __forceinline__ uint32_t row_of(const uint32_t* __restrict__ off, uint32_t lo,
-                                           uint32_t hi, uint32_t q) {
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-    if (off[mid] <= q) lo = mid;
-    else hi = mid - 1u;
-  }
-  return lo;
-}
-
 struct Token {
   uint64_t id;
   uint32_t cnt;     // the row's members, when this entry leads the row (else 0)

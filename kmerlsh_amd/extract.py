@@ -13,8 +13,9 @@ Reference interface mirrored (same names and argument meaning):
   void IOFQ::Extracting(vector<string> samples, uset_t*, string out, int num_threads,
                         float kmer_vote, bool verbose)                 io/ioFastQ.cc:161-195
 
-The t-test runs on the host (klsh_wrs: ALGLIB restated, bit-exact); the k-mer vote over the reads
-runs on the GPU (klsh_check_reads / klsh_extract_fastq).  No CPU fallback: without the library or a
+The t-test runs on the host (klsh_wrs: ALGLIB restated, bit-exact); the cluster text is parsed and
+the two k-mer sets are selected on the GPU (differential_ksets: klsh_diff_ksets); the k-mer vote
+over the reads runs on the GPU (klsh_check_reads / klsh_extract_fastq).  No CPU fallback: without the library or a
 gfx950 device every GPU entry point raises.  k-mers are the reference's 8-byte Kmer images as
 little-endian uint64 (kmer_set.hex layout, kmer/Kmer.cc:307).
 """
@@ -70,6 +71,18 @@ def wrs_all(abundances, num_sample1: int, num_sample2: int, pvalue_thresh: float
         elif gg == 2:
             g2.update(a._ids)
     return g1, g2
+
+
+def differential_ksets(engine: "_native.Engine", num_sample1: int, num_sample2: int,
+                       pvalue_thresh: float, size_thresh: int, kmap_size: int,
+                       file_name: str = "clustering_result.txt", kmer_set: str = "kmer_set.hex"):
+    """ReadClusterAll + WRS over every cluster + the two uset_t of app/kmerLSH.cc:541-585 in one
+    library call on the device (klsh_diff_ksets): (set A, set B, statistics).  The sets are
+    ``_native.KmerSet`` objects for CheckRead / ReadExtract / Extracting; statistics["ids_a"] /
+    ["ids_b"] are the reference's two "# of differential kmers" numbers.  This is the route from
+    cluster files to the sets; ReadClusterAll and wrs_all stay for callers that want the ids."""
+    return _native.diff_ksets(engine, file_name, kmer_set, kmap_size, num_sample1, num_sample2,
+                              pvalue_thresh, size_thresh)
 
 
 def read_kmer_set(kmap_size: int, path: str = "kmer_set.hex") -> np.ndarray:
