@@ -424,6 +424,57 @@ int klsh_parse_clust(klsh_ctx* ctx, const char* text, uint64_t len, int path, ui
                      uint64_t* counts, uint64_t* offsets, uint64_t* ids, uint64_t* n_ids,
                      uint64_t* irregular_at, int* path_used);
 
+/* Plain FASTQ parsed on the device (modes E and K: klsh_extract_fastq, klsh_count_khtable,
+ * klsh_count_kmc).  A plain file is read in chunks, each starting at a record
+ * boundary; lines are split at '\n', record r is lines 4r .. 4r + 3, and a chunk's complete records
+ * are those up to the last newline that ends a line 4r + 3.  Record r is REGULAR when
+ *   L0 begins with '@' (the name is the rest, any bytes);
+ *   L1, the sequence, holds only bytes in [33, 126] other than '>', '+', '@' (it may be empty);
+ *   L2 begins with '+', every further byte below 0x80;
+ *   L3 holds exactly len(L1) bytes, each in [33, 127];
+ * the host reader (klsh_fastq_next) reads such records as exactly these lines.  The kernels parse
+ * the complete records of every chunk whose complete records are all regular; the next chunk starts
+ * after them.  The host reader takes over at a chunk's file offset, and keeps the rest of the
+ * file, when the chunk's complete records hold an irregularity or the chunk holds no complete
+ * record (the bytes after the last complete record of the file; a record longer than a chunk).  A
+ * file that begins with the gzip magic, and a path that is not a regular file (a FIFO, a process
+ * substitution, /dev/stdin: no size, no positioned reads), is read by the host reader alone.  No result depends on any
+ * of this: records, files, listings and statistics are the host reader's.
+ * Options (klsh_set_option):
+ *   "fastq_parse"        0 = the device where it can (the default: DESIGN.md §16.6), 1 = the host
+ *                        reader only, 2 = the device only: KLSH_E_ARG, the message naming the
+ *                        file offset, where the host reader would have to take over (for tests:
+ *                        klsh_extract_fastq then leaves an output file that holds only the
+ *                        records of the chunks finished before the refusal)
+ *   "fastq_chunk_bytes"  bytes per chunk (0 = the default 64 MB; a test hook, in [64, 2^31]:
+ *                        positions inside a chunk are 32-bit)
+ * Read-only, of the context's last klsh_extract_fastq / klsh_count_khtable / klsh_count_kmc call:
+ *   "fastq_device_chunks", "fastq_device_reads", "fastq_host_reads" (the two add up to the call's
+ *   reads), "fastq_takeover_at" (the file offset where the host reader started — 0 for a file it
+ *   read whole — in the call's last file that it read any of; all ones (-1) if it read none),
+ *   "fastq_parse_us" (HIP-event time of the parser's kernels), "fastq_read_us" (host time of the
+ *   chunks' file reads), "fastq_tile" (the kernels' tile, bytes).
+ *
+ * klsh_parse_fastq (a test hook) parses one chunk, `text` (len < 2^32 bytes, host memory).  path 0 =
+ * the kernels, 1 = the host reader over the same bytes.
+ *   *n_records    path 0: the complete records, 0 when they are not all regular; path 1: the
+ *                 records the reader read (it also reads what follows the complete records)
+ *   line_starts   4 n + 1 entries: the offset of each line's first byte, the last = *consumed
+ *                 (path 1: the lines of the bytes it consumed, all ones where those are fewer)
+ *   seq_off, seq  n + 1 offsets and the sequences they delimit, as klsh_check_reads takes them
+ *   *seq_cap      in: the capacity of seq; out: the bases (KLSH_E_RANGE if seq is too small)
+ *   *consumed     path 0: the end of the last complete record, 0 when the chunk is irregular;
+ *                 path 1: the end of the last record read
+ *   *irregular_at path 0: the smallest offset that makes a complete record irregular, all ones if
+ *                 none does.  A byte outside its line's class is its own offset; an empty L0 or L2
+ *                 is the offset of its newline; an L3 of another length than L1 is
+ *                 (start of L3) + min(len(L1), len(L3)): the newline that came too early, or the
+ *                 first byte too many.  path 1: all ones (the reader does not classify).
+ * The three arrays may be NULL (a size query); every other out-pointer is required. */
+int klsh_parse_fastq(klsh_ctx* ctx, const char* text, uint64_t len, int path, uint64_t* n_records,
+                     uint32_t* line_starts, uint64_t* seq_off, char* seq, uint64_t* seq_cap,
+                     uint64_t* consumed, uint64_t* irregular_at);
+
 /* ---- mode E: differential k-mers and read extraction (reference app/kmerLSH.cc:521-580) ------- */
 /* AB::WRS (reference function/funcAB.cc:73-109) for every cluster at once: a cluster with more than
  * size_thresh members (member_counts[c]) is tested with ALGLIB's pooled two-sample Student t-test

@@ -40,7 +40,7 @@ EXPORTED = (
     "klsh_count_khtable", "klsh_kcount_listing", "klsh_count_kmc",
     "klsh_load_rows_device", "klsh_result_device", "klsh_labels",
     "klsh_load_clusters_device", "klsh_save_clusters", "klsh_kset_find", "klsh_tail_buckets",
-    "klsh_diff_ksets", "klsh_parse_clust",
+    "klsh_diff_ksets", "klsh_parse_clust", "klsh_parse_fastq",
 )
 
 
@@ -297,6 +297,8 @@ def load_library() -> ctypes.CDLL:
                                            ctypes.POINTER(_P), ctypes.POINTER(_P), _P]),
         "klsh_parse_clust": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int, _u64p, _P, _P,
                                             _P, _u64p, _u64p, ctypes.POINTER(ctypes.c_int)]),
+        "klsh_parse_fastq": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int, _u64p, _P, _P, _P,
+                                            _u64p, _u64p, _u64p]),
         "klsh_build_khtable": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
                                               ctypes.c_int, ctypes.c_char_p, _P]),
         "klsh_cuckoo_order": (ctypes.c_int, [_P, ctypes.c_uint64, ctypes.c_int, _P]),
@@ -568,6 +570,37 @@ def parse_clust(engine: "Engine", text: bytes, path: int = 0, ids: bool = True) 
     out.update(n_lines=int(n_lines.value), n_ids=int(n_ids.value), path_used=int(used.value),
                irregular_at=None if irr.value == 2**64 - 1 else int(irr.value))
     return out
+
+
+def parse_fastq(engine: "Engine", data: bytes, path: int = 0, seq_capacity: int | None = None) -> dict:
+    """``klsh_parse_fastq`` (a test hook): one chunk of plain FASTQ parsed by the kernels (path 0)
+    or read by the host reader (path 1).  Returns n_records, line_starts (uint32, 4 n + 1), seq_off
+    (uint64, n + 1), seq (bytes), consumed and irregular_at (None if nothing is irregular).
+    seq_capacity: None = a size query (NULL arrays) and then the call with arrays of those sizes;
+    a number = one call with a sequence buffer of that many bytes and offset arrays for as many
+    records as the data can hold."""
+    lib = engine._lib
+    buf = np.frombuffer(bytes(data) + b"\0", np.uint8)
+    n, cap, used, irr = (ctypes.c_uint64(0) for _ in range(4))
+
+    def call(lines, off, seq):
+        _check(lib.klsh_parse_fastq(engine._ctx, _ptr(buf), len(data), int(path), ctypes.byref(n),
+                                    _ptr(lines), _ptr(off), _ptr(seq), ctypes.byref(cap),
+                                    ctypes.byref(used), ctypes.byref(irr)), "klsh_parse_fastq")
+
+    if seq_capacity is None:
+        call(None, None, None)
+        nr, nb = n.value, cap.value
+    else:  # (the reader reads a record per header line at most, and one without any)
+        nr, nb = bytes(data).count(b"\n") + 1, int(seq_capacity)
+    # (one entry more: no empty array's NULL pointer)
+    lines, off, seq = np.zeros(4 * nr + 1, np.uint32), np.zeros(nr + 1, np.uint64), np.zeros(nb + 1, np.uint8)
+    cap.value = nb
+    call(lines, off, seq)
+    nr, nb = n.value, cap.value
+    return dict(n_records=int(nr), line_starts=lines[:4 * nr + 1], seq_off=off[:nr + 1],
+                seq=seq[:nb].tobytes(), consumed=int(used.value),
+                irregular_at=None if irr.value == 2**64 - 1 else int(irr.value))
 
 
 class Engine:

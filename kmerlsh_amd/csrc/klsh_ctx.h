@@ -234,6 +234,25 @@ struct DiffHooks {
   uint64_t chunk_bytes = 0;  // "diff_chunk_bytes": bytes per host-to-device chunk (0 = 64 MB)
 };
 
+// The device FASTQ parser's options and what the context's last mode-E / mode-K call reached
+// (klsh_options.cpp, klsh_fastq.cpp)
+struct FastqHooks {
+  int parse = 0;               // "fastq_parse": 0 = auto (device, host on a takeover; the default
+                               // by the measurement of DESIGN.md §16.6), 1 = host
+                               // reader only, 2 = device only (a takeover is an error)
+  uint64_t chunk_bytes = 0;    // "fastq_chunk_bytes": bytes per chunk (0 = 64 MB)
+  uint64_t device_chunks = 0;  // "fastq_device_chunks"
+  uint64_t device_reads = 0;   // "fastq_device_reads"
+  uint64_t host_reads = 0;     // "fastq_host_reads"
+  uint64_t takeover_at = ~0ull;  // "fastq_takeover_at": the file offset the host reader started at
+  double parse_ms = 0.0;       // "fastq_parse_us": HIP-event time of the parser's kernels
+  double read_ms = 0.0;        // "fastq_read_us": host time of the chunks' positioned file reads
+};
+
+// klsh_extract.cpp: the reader of klsh_fastq_open on a plain file from byte `offset` on, a record
+// boundary (the host takeover of the device parser)
+klsh_fastq* fastq_open_at(const char* path, uint64_t offset, int* err);
+
 // klsh_result_host.cpp: the kernels of klsh_result.hip over the live order (see there)
 int device_result(klsh_ctx* ctx, uint32_t* d_off, uint32_t* d_nodes, uint32_t* d_labels,
                   uint64_t* total_out);
@@ -392,6 +411,8 @@ struct klsh_ctx {
   klsh::SaveHooks save;
   // klsh_diff_ksets' (klsh_diff.cpp)
   klsh::DiffHooks diff;
+  // the device FASTQ parser's (klsh_fastq.cpp)
+  klsh::FastqHooks fastq;
 
   ~klsh_ctx() { release(); }
 

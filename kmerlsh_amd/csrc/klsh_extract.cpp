@@ -8,15 +8,19 @@
 //                            by the reference, utils/alglib-3.15.0) is restated below in the same
 //                            operation order, with glibc's libm, so the p-values are its bits.
 //   klsh_fastq_*             FastqFile + the reference's kseq variant (utils/fastq.cc,
-//                            kmer/kseq.h:153-200): the exact record rules, gzip or plain.
+//                            kmer/kseq.h:153-200): the exact record rules, gzip or plain
+//                            (klsh_fastq_reader.h).
 //   klsh_kset_* /            IOFQ::CheckRead (io/ioFastQ.cc:5-76) on the GPU (klsh_extract.hip):
 //   klsh_check_reads         the k-mer set as a device hash table, one wave per read.
-//   klsh_extract_fastq       IOFQ::ReadExtract (io/ioFastQ.cc:78-159): parse a batch on the host
-//                            while the GPU checks the previous one, write the selected records.
+//   klsh_extract_fastq       IOFQ::ReadExtract (io/ioFastQ.cc:78-159): a plain file's chunks parsed
+//                            on the device (klsh_fastq.cpp), anything else a batch
+//                            at a time on the host, while the GPU checks the chunk or batch
+//                            before; the selected records written in order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <unistd.h>
 #include <zlib.h>
 
 #include <algorithm>
@@ -25,6 +29,8 @@
 #include <vector>
 
 #include "klsh_ctx.h"
+#include "klsh_fastq_dev.h"
+#include "klsh_fastq_reader.h"
 
 namespace {
 
@@ -385,136 +391,24 @@ void student_t_test2(const double* x, int64_t n, const double* y, int64_t m, dou
   *right = 1 - p;
 }
 
-// ============================================================ FASTQ (the reference's kseq) ====
-// kmer/kseq.h:60-200 as the reference uses it: the name is the whole header line after '@'/'>'
-// (up to '\n'); sequence characters are the isgraph() ones up to the next '>', '+' or '@'; the
-// quality is the next seq.l characters in [33, 127] after the '+' line, plus one more character
-// consumed; a record whose quality is short ends the file (-2).  Characters are read as signed
-// chars, so a 0xFF byte reads as end of input where the reference compares with -1.
-struct FastqReader {
-  gzFile fp = nullptr;
-  std::vector<char> buf;
-  int begin = 0, end = 0;
-  bool is_eof = false;
-  int last_char = 0;
-  bool done = false;
-
-  // batch storage (reader-owned; valid until the next batch)
-  std::vector<char> seq, name, qual;
-  std::vector<uint64_t> seq_off, name_off, qual_off;
-
-  bool open(const char* path) {
-    fp = gzopen(path, "r");
-    if (!fp) return false;
-    (void)gzbuffer(fp, 1 << 20);
-    buf.resize(1 << 20);
-    return true;
-  }
-  ~FastqReader() {
-    if (fp) gzclose(fp);
-  }
-  bool fill() {
-    if (is_eof) return false;
-    begin = 0;
-    end = gzread(fp, buf.data(), (unsigned)buf.size());
-    if (end < (int)buf.size()) is_eof = true;  // a short read is the end (ks_getc)
-    if (end < 0) end = 0;
-    return end > 0;
-  }
-  int getc() {  // ks_getc, kseq.h:60-68
-    if (is_eof && begin >= end) return -1;
-    if (begin >= end && !fill()) return -1;
-    return (int)(signed char)buf[begin++];
-  }
-  // one record appended to the batch: >= 0 (its sequence length), -1 end, -2 truncated
-  int next() {  // kseq_read, kseq.h:153-200
-    int c;
-    if (last_char == 0) {
-      while ((c = getc()) != -1 && c != '>' && c != '@') {
-      }
-      if (c == -1) return -1;
-      last_char = c;
-    }
-    // name: ks_getuntil(ks, '\n', ...) — -1 only when nothing is left
-    if (begin >= end && is_eof) return -1;
-    const size_t n0 = name.size(), s0 = seq.size(), q0 = qual.size();
-    while (true) {
-      if (begin >= end && !fill()) break;
-      const char* b = buf.data() + begin;
-      const void* nl = memchr(b, '\n', (size_t)(end - begin));
-      const int stop = nl ? (int)((const char*)nl - buf.data()) : end;
-      name.insert(name.end(), b, (const char*)buf.data() + stop);
-      begin = stop + (nl ? 1 : 0);
-      if (nl) break;
-    }
-    // (a header line ending at EOF would read a comment here: nothing is left to read)
-    while ((c = getc()) != -1 && c != '>' && c != '+' && c != '@')
-      if (c >= 33 && c <= 126) seq.push_back((char)c);  // isgraph in the C locale
-    if (c == '>' || c == '@') last_char = c;
-    const size_t sl = seq.size() - s0;
-    if (c != '+') {  // no quality: the reference would copy a stale buffer; we keep it empty
-      commit();
-      return (int)sl;
-    }
-    while ((c = getc()) != -1 && c != '\n') {
-    }
-    if (c == -1) {
-      rollback(n0, s0, q0);
-      return -2;
-    }
-    size_t ql = 0;
-    while ((c = getc()) != -1 && ql < sl)
-      if (c >= 33 && c <= 127) {
-        qual.push_back((char)c);
-        ++ql;
-      }
-    last_char = 0;
-    if (sl != ql) {
-      rollback(n0, s0, q0);
-      return -2;
-    }
-    commit();
-    return (int)sl;
-  }
-  void commit() {
-    seq_off.push_back(seq.size());
-    name_off.push_back(name.size());
-    qual_off.push_back(qual.size());
-  }
-  void rollback(size_t n0, size_t s0, size_t q0) {
-    name.resize(n0);
-    seq.resize(s0);
-    qual.resize(q0);
-  }
-  // up to max_reads records (or until ~max_bases sequence bytes): FastqFile::read
-  // (utils/fastq.cc:54-67) with larger parts — part boundaries change nothing downstream.
-  // On a 64-byte boundary: next()'s byte loops are inlined here, and their speed moved with the
-  // function's offset inside a cache line (mode K's parse of 2 x 10^6 reads: 660 ms at offset 0,
-  // 725 ms at offset 16, which is where growth of the objects linked before this one had put it).
-  __attribute__((aligned(64))) uint64_t batch(uint64_t max_reads, uint64_t max_bases) {
-    seq.clear();
-    name.clear();
-    qual.clear();
-    seq_off.assign(1, 0);
-    name_off.assign(1, 0);
-    qual_off.assign(1, 0);
-    uint64_t n = 0;
-    while (!done && n < max_reads && seq.size() < max_bases) {
-      if (next() < 0) {
-        done = true;  // -1 (end) and -2 (truncated record) both end the file (fastq.cc:59-66)
-        break;
-      }
-      ++n;
-    }
-    return n;
-  }
-};
-
 }  // namespace
+
+using klsh::FastqReader;
 
 struct klsh_fastq {
   FastqReader r;
 };
+
+klsh_fastq* klsh::fastq_open_at(const char* path, uint64_t offset, int* err) {
+  klsh_fastq* f = new klsh_fastq();
+  if (!f->r.open_at(path, offset)) {
+    delete f;
+    *err = set_error(KLSH_E_ARG, (std::string("cannot open ") + path).c_str());
+    return nullptr;
+  }
+  *err = KLSH_OK;
+  return f;
+}
 
 extern "C" {
 
@@ -674,8 +568,16 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
   local.struct_size = sizeof(local);
   KLSH_HIP(hipSetDevice(ctx->device));
   const hipStream_t s = ctx->stream;
-  FastqReader rdr;
-  if (!rdr.open(in_path)) return set_error(KLSH_E_ARG, (std::string("cannot open ") + in_path).c_str());
+  // The file's chunks on the device while they are regular; the host reader from
+  // where they are not, or from the start.
+  klsh::FastqChunks::begin_call(ctx);
+  klsh::FastqChunks chunks(ctx);
+  bool on_device = false;
+  if (int e = chunks.open(in_path, &on_device)) return e;
+  // (a file that cannot be read fails before the output is created; not opened for the probe:
+  // opening and closing a FIFO would end its writer)
+  if (!on_device && access(in_path, R_OK) != 0)
+    return set_error(KLSH_E_ARG, (std::string("cannot open ") + in_path).c_str());
   klsh::File of(fopen(out_path, "wb"));
   if (!of) return set_error(KLSH_E_ARG, (std::string("cannot open for writing ") + out_path).c_str());
   // Two batch slots: the host parses batch i+1 (slot (i+1)&1) while the GPU checks batch i.
@@ -687,6 +589,7 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
     klsh::DevBuf<uint8_t> dflag;
     klsh::Event done;  // after the flag copy: finish() waits for this batch only
     uint64_t n = 0;
+    uint64_t cap_flags = kReads;  // entries of dhit, dflag, hflag
   } slot[2];
   int rc = KLSH_OK;
   for (auto& sl : slot) {
@@ -760,9 +663,97 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
       return set_error(KLSH_E_ARG, "extract: write failed");
     return KLSH_OK;
   };
+  // A device chunk: parsed and packed into the slot's batch (the parser returns with the line
+  // starts in pinned memory), then the vote and the flags' copy queued behind it.
+  auto launch_chunk = [&](int si) -> int {
+    Slot& sl = slot[si];
+    if (sl.n > sl.cap_flags) {
+      sl.cap_flags = 0;
+      const uint64_t c = sl.n + sl.n / 4;
+      if (sl.dhit.alloc(c) != hipSuccess || sl.dflag.alloc(c) != hipSuccess || sl.hflag.alloc(c) != hipSuccess)
+        return set_error(KLSH_E_NOMEM, "extract: flag buffers");
+      sl.cap_flags = c;
+    }
+    KLSH_HIP(hipEventRecord(sl.dev.e0, s));
+    klsh::launch_check_reads(sl.dev.seq, sl.dev.off, sl.n, k, kmer_vote, ks->tab, ks->mask, sl.dhit,
+                             sl.dflag, s, ctx->grid_cap);
+    KLSH_HIP(hipGetLastError());
+    KLSH_HIP(hipEventRecord(sl.dev.e1, s));
+    KLSH_HIP(hipMemcpyAsync(sl.hflag, sl.dflag, sl.n, hipMemcpyDeviceToHost, s));
+    KLSH_HIP(hipEventRecord(sl.done, s));
+    return KLSH_OK;
+  };
+  // its flagged records written straight from the pinned raw chunk: lines 4i and 4i + 1 as they
+  // are ('@' name '\n' L1 '\n'), "+\n" whatever L2 held, line 4i + 3
+  auto finish_chunk = [&](int si) -> int {
+    Slot& sl = slot[si];
+    const klsh::FastqSlot& c = chunks.slot[si];
+    KLSH_HIP(hipEventSynchronize(sl.dev.e1));
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, sl.dev.e0, sl.dev.e1);
+    local.kernel_ms += ms;
+    KLSH_HIP(hipEventSynchronize(sl.done));
+    out.clear();
+    const char* raw = reinterpret_cast<const char*>(c.raw.get());
+    const uint32_t* ls = c.hline.get();
+    for (uint64_t i = 0; i < sl.n; ++i) {
+      const uint32_t* l = ls + 4 * i;
+      const uint64_t len = l[2] - l[1] - 1u;
+      if (len == 0) {  // io/ioFastQ.cc:20-24
+        printf("\nabnormal read entry skipped\n");
+        fwrite(raw + l[0] + 1u, 1, l[1] - l[0] - 2u, stdout);
+        printf("\n");
+        local.abnormal += 1;
+        continue;
+      }
+      if (len >= (uint64_t)k + 10u) {
+        local.reads_tested += 1;
+        local.kmers_checked += len - (uint64_t)k + 1u;
+      }
+      if (!sl.hflag[i]) continue;
+      local.reads_extracted += 1;
+      out.insert(out.end(), raw + l[0], raw + l[2]);
+      out.push_back('+');
+      out.push_back('\n');
+      out.insert(out.end(), raw + l[3], raw + l[4]);
+    }
+    if (!out.empty() && fwrite(out.data(), 1, out.size(), of.get()) != out.size())
+      return set_error(KLSH_E_ARG, "extract: write failed");
+    return KLSH_OK;
+  };
   int cur = 0;
-  bool pending = false;
-  while (true) {
+  bool pending = false, host_rest = true;
+  // the device chunks: the file read of chunk i + 1 runs while chunk i is voted on; its upload and
+  // parse queue behind the vote (the parse synchronises the stream), and chunk i is written after
+  while (on_device) {
+    const double tp = now_ms();
+    uint64_t n = 0;
+    bool eof = false;
+    rc = chunks.next(cur, slot[cur].dev, true, false, &n, &eof);
+    local.parse_ms += now_ms() - tp;
+    if (rc) break;
+    if (n > 0) {
+      slot[cur].n = n;
+      local.reads += n;
+      local.bases += chunks.slot[cur].bases;
+      if ((rc = launch_chunk(cur))) break;
+    }
+    if (pending && (rc = finish_chunk(cur ^ 1))) break;
+    pending = n > 0;
+    if (n == 0) {  // the end of the file, or the host reader takes over at chunks.offset()
+      host_rest = !eof;
+      break;
+    }
+    cur ^= 1;
+  }
+  // the host reader: the whole file, or from where it takes over
+  FastqReader rdr;
+  if (rc == KLSH_OK && host_rest && !rdr.open_at(in_path, chunks.offset()))
+    rc = set_error(KLSH_E_ARG, (std::string("cannot open ") + in_path).c_str());
+  cur = 0;
+  pending = false;
+  const uint64_t reads_device = local.reads;
+  while (rc == KLSH_OK && host_rest) {
     const double tp = now_ms();
     const uint64_t n = rdr.batch(kReads, kBases);
     local.parse_ms += now_ms() - tp;
@@ -783,6 +774,7 @@ int klsh_extract_fastq(klsh_ctx* ctx, const klsh_kset* ks, const char* in_path,
     cur ^= 1;
   }
   if (rc == KLSH_OK && pending) rc = finish(cur);
+  chunks.host_reads(local.reads - reads_device);
   if (rc) (void)hipStreamSynchronize(s);  // nothing of this call stays queued on its buffers
   if (fclose(of.release()) != 0 && rc == KLSH_OK) rc = set_error(KLSH_E_ARG, "extract: close failed");
   local.total_ms = now_ms() - t_start;

@@ -585,6 +585,41 @@ void launch_diff_insert(const uint64_t* kmers, const uint8_t* mark_a, const uint
                         uint64_t kmap, uint64_t* tab_a, uint64_t mask_a, uint64_t* tab_b,
                         uint64_t mask_b, hipStream_t s, uint32_t grid_cap = 0);
 
+// ---- plain FASTQ parsed on the device (klsh_fastq.hip) --------------------------
+// A chunk of the file on the device: len < 2^32 bytes in a buffer of fq_text_alloc(len) bytes (the
+// bytes from len on are never looked at).  Record r = lines 4r .. 4r + 3; n = newlines / 4.
+constexpr uint32_t kFqTile = 256 * 16;  // bytes per text tile: 16 aligned bytes per lane
+constexpr uint32_t kFqRecTile = 256;    // records per tile of the record passes
+inline uint64_t fq_tiles(uint64_t len) { return (len + kFqTile - 1) / kFqTile; }
+inline uint64_t fq_text_alloc(uint64_t len) { return (fq_tiles(len) + 1) * kFqTile; }
+inline uint64_t fq_record_tiles(uint64_t n) { return (n + kFqRecTile - 1) / kFqRecTile; }
+// hdr (64-bit words; the caller sets hdr[kFqIrregular] to all ones and zeroes the rest)
+constexpr uint32_t kFqIrregular = 0;  // the smallest offset that makes a complete record irregular
+constexpr uint32_t kFqNewlines = 1;
+constexpr uint32_t kFqRecords = 2;    // newlines / 4
+constexpr uint32_t kFqBases = 3;      // the records' len(L1), summed
+constexpr uint32_t kFqConsumed = 4;   // line_start[4 n]: the end of the last complete record
+constexpr uint32_t kFqHdrWords = 8;
+// tile_nl (fq_tiles(len) words) = the newlines before each tile; hdr[kFqNewlines], hdr[kFqRecords]
+void launch_fq_scan(const uint8_t* txt, uint32_t len, uint32_t* tile_nl, unsigned long long* hdr,
+                    hipStream_t s, uint32_t grid_cap = 0);
+// line_start[l] = the offset of line l's first byte, l <= 4 n_records; the bytes of those lines
+// checked against their kind: hdr[kFqIrregular] = min(itself, the smallest offender)
+void launch_fq_lines(const uint8_t* txt, uint32_t len, const uint32_t* tile_nl, uint32_t n_records,
+                     uint32_t* line_start, unsigned long long* hdr, hipStream_t s,
+                     uint32_t grid_cap = 0);
+// off[r] = the bases before record r, r <= n_records (64-bit, as launch_check_reads and
+// launch_kcount_reads take them); hdr[kFqBases], hdr[kFqConsumed]; a record whose L3 is not as long as its L1 puts
+// line_start[4r + 3] + min(len(L1), len(L3)) into hdr[kFqIrregular].  rec_sum:
+// fq_record_tiles(n_records) words.
+void launch_fq_records(const uint32_t* line_start, uint32_t n_records, uint32_t* rec_sum,
+                       uint64_t* off, unsigned long long* hdr, hipStream_t s, uint32_t grid_cap = 0);
+// seq[off[r] .. off[r + 1]) = record r's L1, unless hdr[kFqIrregular] is set by then; seq holds
+// seq_bytes
+void launch_fq_pack(const uint8_t* txt, uint32_t len, const uint32_t* line_start, const uint64_t* off,
+                    uint32_t n_records, const unsigned long long* hdr, uint8_t* seq,
+                    uint64_t seq_bytes, hipStream_t s, uint32_t grid_cap = 0);
+
 // Floating-point self test: sqrt_out[i] = sqrtf(a[i]); div_out[i] = a[i] / b[i] as the merge
 // kernels evaluate them.
 void launch_fp_selftest(const float* a, const float* b, uint32_t n, float* sqrt_out,

@@ -3,9 +3,11 @@
 // kmc = true, io/ioHT.cc:83-199, which runs `kmc -k<K> -r -cs65535 -ci<C>` per sample and then
 // reads the databases back).
 //
-// Per sample: the host parses a batch of reads (klsh_fastq_next) while the GPU counts the
-// previous one into the sample's hash table (klsh_kcount.hip), which doubles between batches
-// when the next batch could load it past one half.  After the last batch the entries with
+// Per sample: a plain file's chunks are parsed on the device (klsh_fastq.cpp);
+// for gzip, and from a chunk the device leaves to it, the host parses a batch of reads
+// (klsh_fastq_next).  Either way the GPU counts the previous batch meanwhile into the sample's
+// hash table (klsh_kcount.hip), which doubles between batches when the next batch could load it
+// past one half.  After the last batch the entries with
 // count >= count_min are sorted by their KMC value (two stable radix passes, low word then high
 // word): the listing of a KMC1-layout database, the convention of DESIGN.md §8.  The listings
 // stay on the device until every sample is counted; the table build of mode B (klsh::khtable_run,
@@ -25,6 +27,7 @@
 #include <vector>
 
 #include "klsh_ctx.h"
+#include "klsh_fastq_dev.h"
 
 namespace {
 
@@ -233,7 +236,7 @@ class Counter {
  public:
   Counter(klsh_ctx* ctx, int k, uint32_t count_min, klsh_kcount_stats& st)
       : hooks_(ctx->kcount), s_(ctx->stream), k_(k), count_min_(count_min),
-        st_(st) {}
+        st_(st), chunks_(ctx) {}
   int init() {
     cap_ = hooks_.table_slots ? hooks_.table_slots : kTableSlots;
     hooks_.peak_slots = cap_;
@@ -249,12 +252,30 @@ class Counter {
   // path's reads counted, the listing left in *out
   int sample(const char* path, Listing* out, std::vector<uint64_t>* keep_val,
              std::vector<uint32_t>* keep_cnt) {
-    int err = KLSH_OK;
-    klsh_fastq* f = klsh_fastq_open(path, &err);
-    if (!f) return err;
-    const int rc = count(f);
-    klsh_fastq_close(f);
-    if (rc) return rc;
+    // the file's chunks on the device while they are regular, the host reader from
+    // where they are not, or from the start
+    occ_ = pos_ = 0;
+    KLSH_HIP(hipMemsetAsync(keys_, 0xFF, cap_ * 8, s_));
+    KLSH_HIP(hipMemsetAsync(cnt_, 0, cap_ * 4, s_));
+    KLSH_HIP(hipMemsetAsync(ctr_, 0, 64, s_));
+    bool on_device = false, host_rest = true;
+    if (int rc = chunks_.open(path, &on_device)) return rc;
+    if (on_device) {
+      if (int rc = count_chunks(&host_rest)) {
+        (void)hipStreamSynchronize(s_);
+        return rc;
+      }
+    }
+    if (host_rest) {
+      int err = KLSH_OK;
+      klsh_fastq* f = klsh::fastq_open_at(path, chunks_.offset(), &err);
+      if (!f) return err;
+      const uint64_t before = st_.reads;
+      const int rc = count(f);
+      klsh_fastq_close(f);
+      chunks_.host_reads(st_.reads - before);
+      if (rc) return rc;
+    }
     return list(out, keep_val, keep_cnt);
   }
   // the KMC values of the last sample's listing (device), until the next sample is listed
@@ -276,6 +297,7 @@ class Counter {
   DevBuf<uint64_t> keys_, ctr_, val_;
   DevBuf<uint32_t> cnt_, lo_, lo2_, sl_, sl2_, ws_;
   uint64_t sort_cap_ = 0;
+  klsh::FastqChunks chunks_;
 
   // the table doubled until `more` further k-mers keep it at most half full
   int grow(uint64_t more) {
@@ -329,11 +351,60 @@ class Counter {
     return KLSH_OK;
   }
 
+  // The device chunks of the open file: each parsed and packed into its slot's batch, then counted
+  // by the protocol of count() below, a launch per `per` reads at an offset into the chunk's
+  // offsets.  The next chunk's file read runs while the last launch of this one does; its upload
+  // and parse queue behind that launch (the parse synchronises the stream).
+  // *host_rest = the host reader has the rest of the file to read, from chunks_.offset().
+  int count_chunks(bool* host_rest) {
+    const uint64_t per = hooks_.batch_reads ? hooks_.batch_reads : kBatchReads;
+    int cur = 0;
+    bool pending = false;
+    while (true) {
+      const double tp = now_ms();
+      Slot& sl = slot_[cur];
+      uint64_t n = 0;
+      bool eof = false;
+      if (int rc = chunks_.next(cur, sl.dev, false, true, &n, &eof)) return rc;
+      st_.parse_ms += now_ms() - tp;
+      if (n == 0) {
+        if (pending) {
+          if (int rc = finish(slot_[cur ^ 1])) return rc;
+        }
+        *host_rest = !eof;
+        return KLSH_OK;
+      }
+      st_.reads += n;
+      st_.bases += chunks_.slot[cur].bases;
+      const uint64_t* off = chunks_.slot[cur].hoff.get();
+      for (uint64_t r0 = 0; r0 < n; r0 += per) {
+        const uint64_t m = std::min<uint64_t>(per, n - r0);
+        uint64_t windows = 0;  // an upper bound of the launch's new k-mers
+        for (uint64_t i = r0; i < r0 + m; ++i) {
+          const uint64_t len = off[i + 1] - off[i];
+          if (len >= (uint64_t)k_) windows += len - (uint64_t)k_ + 1;
+        }
+        if (pending) {  // (the first launch of a chunk waits for the last of the chunk before)
+          if (int rc = finish(r0 ? sl : slot_[cur ^ 1])) return rc;
+        }
+        pending = false;
+        if (int rc = grow(windows)) return rc;
+        KLSH_HIP(hipEventRecord(sl.dev.e0, s_));
+        klsh::launch_kcount_reads(sl.dev.seq, sl.dev.off.get() + r0, m, k_, keys_, cnt_, cap_ - 1, ctr_,
+                                  s_, hooks_.grid_cap);
+        KLSH_HIP(hipGetLastError());
+        KLSH_HIP(hipEventRecord(sl.dev.e1, s_));
+        KLSH_HIP(hipMemcpyAsync(hctr_, ctr_, 16, hipMemcpyDeviceToHost, s_));
+        pending = true;
+        hooks_.batches += 1;
+        st_.batches += 1;
+      }
+      cur ^= 1;
+    }
+  }
+
+  // the reads of the host reader, from where it stands
   int count(klsh_fastq* f) {
-    occ_ = pos_ = 0;
-    KLSH_HIP(hipMemsetAsync(keys_, 0xFF, cap_ * 8, s_));
-    KLSH_HIP(hipMemsetAsync(cnt_, 0, cap_ * 4, s_));
-    KLSH_HIP(hipMemsetAsync(ctr_, 0, 64, s_));
     const uint64_t per = hooks_.batch_reads ? hooks_.batch_reads : kBatchReads;
     int cur = 0, rc = KLSH_OK;
     bool pending = false;
@@ -462,6 +533,7 @@ int count_run(klsh_ctx* ctx, const char* const* fastq_paths, const char* const* 
   hooks.batches = hooks.rehashes = hooks.peak_slots = 0;
   hooks.db_chunks = 0;
   hooks.db_prefix_used = -1;
+  klsh::FastqChunks::begin_call(ctx);
   hooks.values.clear();
   hooks.counts.clear();
   bhooks.decode_launches = 0;

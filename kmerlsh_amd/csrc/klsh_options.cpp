@@ -134,6 +134,23 @@ const Option kOptions[] = {
         c->diff.chunk_bytes = (uint64_t)v;
         return 0;)},
     READONLY("diff_tile_bytes", klsh::kDiffTile),
+    {"fastq_parse", GET(c->fastq.parse), SET(
+        if (v < 0 || v > 2) return out_of_range("fastq_parse", "0 (auto), 1 (host) or 2 (device only)");
+        c->fastq.parse = (int)v;
+        return 0;)},
+    // (positions inside a chunk are 32-bit)
+    {"fastq_chunk_bytes", GET(c->fastq.chunk_bytes), SET(
+        if (v != 0 && (v < 64 || v > (1ll << 31)))
+          return out_of_range("fastq_chunk_bytes", "0 or in [64, 2^31]");
+        c->fastq.chunk_bytes = (uint64_t)v;
+        return 0;)},
+    READONLY("fastq_device_chunks", c->fastq.device_chunks),
+    READONLY("fastq_device_reads", c->fastq.device_reads),
+    READONLY("fastq_host_reads", c->fastq.host_reads),
+    READONLY("fastq_takeover_at", c->fastq.takeover_at),
+    READONLY("fastq_parse_us", c->fastq.parse_ms * 1000.0),
+    READONLY("fastq_read_us", c->fastq.read_ms * 1000.0),
+    READONLY("fastq_tile", klsh::kFqTile),
     READONLY("save_chunks", c->save.chunks),
     READONLY("save_ids_uploaded", c->save.ids_uploaded),
     GRID("h16_grid", pp.h16_grid),
